@@ -2,6 +2,7 @@
 """bench.py -- headline benchmark of the perfect-tandem-repeat scan on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hg38|chr22|chr22-real|chr1|random|hg38-random]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one complete scan of the workload for every motif size in [kmin,kmax]: two back-to-back launches on one stream
@@ -28,8 +29,15 @@ completed when the timed region ends).
 
 Rank 0 prints ONE JSON line.  `value` is whole-job Gbp/s from the wall clock (max over ranks); the `roofline` object prices
 the dominant kernel (prf_vscan_kernel) with the HIP events recorded around each of its launches in the timed region on the
-library's stream (read after the loop, prf_scan_timings_split); `cpu_baseline` is the CPU oracle (a C restatement of the
-reference, oracle/prf_oracle.c) timed on a bounded sample of the same workload on this host: one thread, and all host cores.
+library's stream (read after the loop, prf_scan_timings_split).
+
+--full adds what takes runs of its own: `cpu_baseline`, the CPU oracle (a C restatement of the reference,
+oracle/prf_oracle.c) timed on a bounded sample of the same workload on this host (one thread, and all host cores; not with
+--no-cpu-baseline), and `roofline.measured_hbm_read_GBps`, a read of 1 GiB on the device (null without --full).
+
+--dump-outputs DIR writes, after the timed steps, the rows the last timed scan returned (at N > 1: the rows rank 0 received
+with the last gather) as float64 .npy files: per contig the row count and the sums of start, end and motif size, and a fixed,
+seeded sample of at most 2^20 rows with their indices in the sorted row array (dump_outputs).
 """
 import argparse
 import json
@@ -67,6 +75,50 @@ def pmc_record(workload, kmin, kmax):
     except (ValueError, KeyError):
         pass
     return None
+
+
+DUMP_SAMPLE_ROWS = 1 << 20   # 40 MiB of float64 with the indices: the dump stays under 64 MB
+DUMP_SAMPLE_SEED = 2026
+
+
+def last_rows(ctx, n_rows, dtype, scan):
+    """The rows of the last scan collected on this context, copied off the device (prf_last_hits_to_device), sorted by
+    (contig, start, end) as Genome.scan returns them.  The literal lane (min_repeats 1) hands its rows over on the host
+    only: for it the scan runs once more, untimed, and its rows are fetched."""
+    import numpy as np
+    import torch
+    buf = torch.empty((max(1, n_rows), 3), dtype=torch.int64, device="cuda")   # 24-byte records
+    n = ctx.last_hits_to_device(buf.data_ptr(), n_rows)
+    if n == 0 < n_rows:
+        rows, _ = scan(True)
+        assert len(rows) == n_rows, (len(rows), n_rows)
+        return rows
+    assert n == n_rows, (n, n_rows)
+    rows = np.ascontiguousarray(buf.cpu().numpy()[:n]).view(dtype).reshape(-1)
+    return rows[np.lexsort((rows["end"], rows["start"], rows["contig"]))]
+
+
+def dump_outputs(out_dir, rows, n_contigs):
+    """rows (start, end, k, contig), sorted -> out_dir/*.npy, float64 (positions < 2^53 are exact):
+    contig_totals: [rows, sum of start, sum of end, sum of k] per contig (sums taken in uint64, then converted);
+    rows_sample: [contig, start, end, k] of at most DUMP_SAMPLE_ROWS rows drawn with a fixed seed, in row order;
+    rows_sample_index: their indices in the sorted row array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    contig = rows["contig"]
+    totals = np.zeros((n_contigs, 4), dtype=np.float64)
+    for c in range(n_contigs):
+        lo, hi = np.searchsorted(contig, c, "left"), np.searchsorted(contig, c, "right")
+        totals[c] = [hi - lo] + [float(rows[f][lo:hi].sum(dtype=np.uint64)) for f in ("start", "end", "k")]
+    n = len(rows)
+    if n > DUMP_SAMPLE_ROWS:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_SAMPLE_ROWS, replace=False))
+    else:
+        idx = np.arange(n)
+    sample = np.stack([rows[f][idx].astype(np.float64) for f in ("contig", "start", "end", "k")], axis=1).reshape(-1, 4)
+    np.save(os.path.join(out_dir, "contig_totals.npy"), totals)
+    np.save(os.path.join(out_dir, "rows_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "rows_sample_index.npy"), idx.astype(np.float64))
 
 
 def _oracle_chunk(job):
@@ -249,7 +301,14 @@ def main():
                          "raises its clock over the first tens of milliseconds of sustained load (DVFS) and the scan is VALU-bound -- "
                          "per-step kernel time falls from 0.66 to 0.53 ms over 40 steps from an idle GPU.  0: none")
     ap.add_argument("--gather-every", type=int, default=1, help="N>1: gather the rows to rank 0 every this many steps (0: never)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the rows of the last one to DIR/*.npy (float64; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU oracle baseline (cpu_baseline) and the device's "
+                         "HBM read rate (roofline.measured_hbm_read_GBps)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if not args.kmax:
         args.kmax = 100 if args.workload == "random" else 50
 
@@ -438,6 +497,8 @@ def main():
             seqs.append(st.seq)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and world == 1:
+        dump_outputs(args.dump_outputs, last_rows(ctx, n_rows_local, rows.dtype, scan), len(lens))
     scan_ms = gather_kernel_ms = None
     if st0.path == 1 and st0.n_launches:
         # fused path: kernel durations from the HIP events recorded around each launch of the timed region (the
@@ -474,6 +535,10 @@ def main():
         parts = [multi_gpu.unpack_rows(r.cpu().numpy(), gather_cap, SIDE, bases, prf_native.tile_positions()) for r in recv]
         got = np.concatenate(parts)
         gathered_ok = bool(len(got) == n_rows_total and np.array_equal(got, rows_whole))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, got, len(lens))
+    elif world > 1 and rank == 0 and args.dump_outputs:
+        raise SystemExit("--dump-outputs at N > 1 writes the rows of the last gather: none was made (--gather-every)")
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = total_bp / (elapsed / args.steps) / 1e9
@@ -485,7 +550,7 @@ def main():
         t_scan = both_ms if st0.path == 1 else p1
         achieved = bytes_alg / (t_scan * 1e-3) / 1e9 if t_scan else 0.0
         achieved_scan_only = bytes_alg / (p1 * 1e-3) / 1e9 if p1 else 0.0
-        hbm_meas = ctx.measure_hbm_read(1 << 30, 5)
+        hbm_meas = ctx.measure_hbm_read(1 << 30, 5) if args.full else None
         pmc = pmc_record(args.workload, args.kmin, args.kmax) if (st0.path == 1 and world == 1) else None
         out = {
             "metric": f"Gbp/s scanned (motif {args.kmin}-{args.kmax})", "value": round(value, 4), "unit": "Gbp/s", "n_gpus": world,
@@ -530,10 +595,10 @@ def main():
                          "algorithmic_bytes_per_launch": bytes_alg,
                          # the same counting only the tiles that are launched (tiles of nothing but N are skipped)
                          "achieved_nonN": round(((int(st0.tiles_launched) * 65536) // 4 + 24 * n_rows_local) / (t_scan * 1e-3) / 1e9, 2) if t_scan else None,
-                         "measured_hbm_read_GBps": round(hbm_meas, 1),
-                         "frac_of_measured_read": round(achieved / hbm_meas, 5)},
+                         "measured_hbm_read_GBps": round(hbm_meas, 1) if hbm_meas else None,
+                         "frac_of_measured_read": round(achieved / hbm_meas, 5) if hbm_meas else None},
         }
-        if not args.no_cpu_baseline and world == 1:   # the CPU baseline is timed on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # the CPU baseline is timed on rank 0 at N=1 only
             n = min(args.cpu_sample_bp, lens[0] - 20_000) if lens[0] > 40_000 else lens[0]
             out["cpu_baseline"] = cpu_baseline(sample_fn(n), args.kmin, args.kmax, args.min_repeats, args.min_span,
                                                (sample_what % n) + " of the workload")

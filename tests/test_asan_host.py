@@ -28,9 +28,12 @@ def test_host_code_under_address_and_undefined_behaviour_sanitizers(tmp_path):
     if not os.path.exists(oracle_lib) or os.path.getmtime(oracle_lib) < os.path.getmtime(src):
         subprocess.check_call(["gcc", "-O1", "-g", "-std=c11", "-fPIC", "-shared", "-Wall", "-fsanitize=address,undefined",
                                "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined", "-o", oracle_lib, src])
-    env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
+    preload = " ".join([asan] + os.environ.get("LD_PRELOAD", "").split())   # the ASan runtime first, what was preloaded kept
+    env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
                PRF_LIB=host_lib, PRF_LIB_HOST_ONLY="1", PRF_ORACLE_LIB=oracle_lib)
-    cmd = [sys.executable, "-m", "pytest", "-q", "-x", "-p", "no:cacheprovider",
+    # --rootdir: otherwise pytest roots the child at the common ancestor of its cwd (tmp_path) and the tests, a directory the
+    # test user may not be allowed to list
+    cmd = [sys.executable, "-m", "pytest", "-q", "-x", "-p", "no:cacheprovider", "--rootdir", ROOT,
            os.path.join(ROOT, "tests", "test_fasta_io.py"), os.path.join(ROOT, "tests", "test_plan.py"),
            os.path.join(ROOT, "tests", "test_oracle_golden.py")]
     res = subprocess.run(cmd, env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=900)

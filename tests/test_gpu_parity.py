@@ -7,6 +7,9 @@ import os
 
 import numpy as np
 import pytest
+# At collection, before any test of the session runs: a CPU test that loads libprf first (test_abi.py) would bring in the
+# system HIP runtime, and torch would then find no device (see ctx).
+import torch  # noqa: F401
 
 from conftest import GOLDEN
 from helpers import expected, outcome
