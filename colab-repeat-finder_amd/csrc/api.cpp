@@ -28,24 +28,27 @@ static thread_local std::string g_err;
 
 static const u64 PRF_FRONT_PAD = 8;  // readable words in front of every linear plane (X = all ones there)
 
-static int fail(int code, const char *fmt, ...) {
+static int vfail(int code, const char *fmt, va_list ap) {
     char buf[512];
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    g_err = buf;
+    return code;
+}
+
+static int fail(int code, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    vfail(code, fmt, ap);
     va_end(ap);
-    g_err = buf;
     return code;
 }
 
 // for the other host-side translation units of the library
 int prf_set_error(int code, const char *fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    vfail(code, fmt, ap);
     va_end(ap);
-    g_err = buf;
     return code;
 }
 
@@ -56,6 +59,30 @@ int prf_set_error(int code, const char *fmt, ...) {
             return fail(e_ == hipErrorOutOfMemory ? PRF_ENOMEM : PRF_EHIP, "%s failed: %s (%s:%d)", #expr,    \
                         hipGetErrorString(e_), __FILE__, __LINE__);                                           \
     } while (0)
+
+// The C boundary: no exception leaves the library
+template <class F>
+static int guarded(const char *name, F &&f) {
+    try {
+        return f();
+    } catch (const std::bad_alloc &) {
+        return fail(PRF_ENOMEM, "%s: out of host memory", name);
+    } catch (...) {
+        return fail(PRF_EHIP, "%s: unexpected exception", name);
+    }
+}
+
+// A device array of at least `want` elements; a smaller one is replaced (its contents are not kept)
+template <class T>
+static int grow(T *&p, u64 &cap, u64 want) {
+    if (want <= cap) return PRF_OK;
+    (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    HIPCHK(hipMalloc((void **)&p, want * sizeof(T)));
+    cap = want;
+    return PRF_OK;
+}
 
 struct prf_ctx {
     int dev = -1;
@@ -81,7 +108,11 @@ struct prf_ctx {
     u64 hit_cap = 0;
     prf_hit_dev *sink = nullptr;    // caller-owned device array the rows go to instead (prf_set_row_sink)
     u64 sink_cap = 0;
-    const prf_hit_dev *last_rows = nullptr;  // where the rows of the last scan are
+    struct last_scan {              // where the rows of the last scan are
+        const prf_hit_dev *rows = nullptr;
+        u64 nhits = 0;
+        u32 kmax = 0;               // its largest motif size (the 8-byte wire rows hold 9 bits)
+    } last;
     // pipelined scans (prf_scan_genome_async / prf_scan_wait): two slots used alternately, each with its own host
     // counter block and row array; slot 0 shares them with the synchronous path
     struct async_slot {
@@ -104,12 +135,8 @@ struct prf_ctx {
     u32 *d_block_sum = nullptr;     // rows per PRF_GATHER_SLOTS launch slots; zero between scans (the gather clears it)
     u64 slab_slots = 0;
     u32 slab_cap = 0;
-    bool last_sorted = true;        // the rows of the last scan left the device sorted by (contig, start, end)
     u64 *stamps_buf = nullptr;      // diagnostic (PRF_STAMPS) builds only
     u32 stamps_n = 0;
-    // where the rows of the last scan are
-    u64 last_nhits = 0;
-    u32 last_kmax = 0;              // largest motif size of the last scan (the 8-byte wire rows hold 9 bits)
 };
 
 struct prf_genome {
@@ -205,20 +232,13 @@ void prf_close(prf_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->dev);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->d_counters);
     (void)hipHostFree(c->h_counters);
     (void)hipHostFree(c->h_async);
-    (void)hipFree(c->d_hits_async);
-    (void)hipFree(c->d_vcounters);
-    (void)hipFree(c->d_side_cnt);
-    (void)hipFree(c->lit_scratch);
+    for (void *p : {(void *)c->d_counters, (void *)c->d_hits_async, (void *)c->d_vcounters, (void *)c->d_side_cnt, c->lit_scratch,
+                    (void *)c->d_cand, (void *)c->d_hits, (void *)c->d_slabs, (void *)c->d_long_ends, (void *)c->d_slab_count,
+                    (void *)c->d_block_sum})
+        (void)hipFree(p);
     if (c->ev_handoff) (void)hipEventDestroy(c->ev_handoff);
-    (void)hipFree(c->d_cand);
-    (void)hipFree(c->d_hits);
-    (void)hipFree(c->d_slabs);
-    (void)hipFree(c->d_long_ends);
-    (void)hipFree(c->d_slab_count);
-    (void)hipFree(c->d_block_sum);
     for (auto &ev : c->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->ring)
@@ -230,23 +250,57 @@ void prf_close(prf_ctx *c) {
 void prf_genome_free(prf_genome *g) {
     if (!g) return;
     if (g->ctx) (void)hipSetDevice(g->ctx->dev);
-    if (g->H) (void)hipFree(g->H - PRF_FRONT_PAD);
-    if (g->L) (void)hipFree(g->L - PRF_FRONT_PAD);
-    if (g->X) (void)hipFree(g->X - PRF_FRONT_PAD);
-    for (u64 *e : g->E)
-        if (e) (void)hipFree(e - PRF_FRONT_PAD);
-    (void)hipFree(g->d_E);
-    (void)hipFree(g->d_base);
-    (void)hipFree(g->d_tile_info);
-    (void)hipFree(g->vp.VH);
-    (void)hipFree(g->vp.VL);
-    (void)hipFree(g->vp.tile_class);
-    (void)hipFree(g->vp.launch_list);
-    (void)hipFree(g->d_sel_list);
+    for (u64 *plane : {g->H, g->L, g->X, g->E[0], g->E[1], g->E[2], g->E[3], g->E[4]})
+        if (plane) (void)hipFree(plane - PRF_FRONT_PAD);
+    for (void *p : {(void *)g->d_E, (void *)g->d_base, (void *)g->d_tile_info, (void *)g->vp.VH, (void *)g->vp.VL,
+                    (void *)g->vp.tile_class, (void *)g->vp.launch_list, (void *)g->d_sel_list})
+        (void)hipFree(p);
     delete g;
 }
 
 uint64_t prf_genome_positions(const prf_genome *g) { return g ? g->positions : 0; }
+
+// One linear plane of the genome: PRF_FRONT_PAD readable words in front of it, padw behind it, both filled with `pad`
+static int alloc_plane(prf_ctx *c, const prf_genome *g, u64 **plane, int pad) {
+    u64 *p = nullptr;
+    HIPCHK(hipMalloc((void **)&p, (PRF_FRONT_PAD + g->nwords + g->padw) * 8));
+    *plane = p + PRF_FRONT_PAD;
+    HIPCHK(hipMemsetAsync(p, pad, PRF_FRONT_PAD * 8, c->stream));
+    HIPCHK(hipMemsetAsync(*plane + g->nwords, pad, g->padw * 8, c->stream));
+    return PRF_OK;
+}
+
+// The contig of every tile (contigs start on tile boundaries; the gap tiles behind a contig count as its own)
+static int upload_tile_info(prf_genome *g) {
+    const u64 ntiles = g->G / PRF_TILE;
+    std::vector<uint4> info(ntiles, make_uint4(0, 0, 0, 0));
+    for (size_t ci = 0; ci < g->base.size(); ci++) {
+        const u64 t0 = g->base[ci] / PRF_TILE, t1 = ci + 1 < g->base.size() ? g->base[ci + 1] / PRF_TILE : ntiles;
+        for (u64 t = t0; t < t1; t++) info[t] = make_uint4((u32)ci, 0u, (u32)g->base[ci], (u32)(g->base[ci] >> 32));
+    }
+    HIPCHK(hipMalloc((void **)&g->d_tile_info, sizeof(uint4) * ntiles));
+    HIPCHK(hipMemcpy(g->d_tile_info, info.data(), sizeof(uint4) * ntiles, hipMemcpyHostToDevice));
+    return PRF_OK;
+}
+
+// Letters other than A, C, G, T, N: the planes of their codes, and the tile ranges the generic kernels take
+static int load_exotic(prf_ctx *c, prf_genome *g, const uint8_t *asc) {
+    for (u64 *&plane : g->E) {
+        const int rc = alloc_plane(c, g, &plane, 0);
+        if (rc) return rc;
+    }
+    HIPCHK(prf_launch_pack_exotic(c->stream, asc, g->nwords, g->E));
+    HIPCHK(hipMalloc((void **)&g->d_E, 5 * sizeof(u64 *)));
+    HIPCHK(hipMemcpyAsync(g->d_E, g->E, 5 * sizeof(u64 *), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const std::vector<unsigned char> &cls = g->vp.h_class;
+    for (u64 t = 0; t + 1 < cls.size(); t++) {
+        if (cls[t] != 3) continue;
+        if (!g->exotic_tiles.empty() && g->exotic_tiles.back().second == t) g->exotic_tiles.back().second = t + 1;
+        else g->exotic_tiles.emplace_back(t, t + 1);
+    }
+    return PRF_OK;
+}
 
 // contigs[i].ascii == nullptr with seeds != nullptr: contig i is generated on the device from seeds[i]
 // recipe (with seeds): 1 = uniform background, 2 = stand-in recipe 2 (N blocks + planted repeats)
@@ -297,45 +351,22 @@ static int genome_load_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs
         else
             HIPCHK(hipMemcpyAsync(asc + g->base[i], contigs[i].ascii, contigs[i].len, hipMemcpyHostToDevice, c->stream));
     }
-    const u64 tot = PRF_FRONT_PAD + g->nwords + g->padw;
-    {
-        u64 *p = nullptr;
-        HIPCHK(hipMalloc((void **)&p, tot * 8));
-        g->H = p + PRF_FRONT_PAD;
-        HIPCHK(hipMalloc((void **)&p, tot * 8));
-        g->L = p + PRF_FRONT_PAD;
-        HIPCHK(hipMalloc((void **)&p, tot * 8));
-        g->X = p + PRF_FRONT_PAD;
-    }
-    HIPCHK(hipMemsetAsync(g->H - PRF_FRONT_PAD, 0, PRF_FRONT_PAD * 8, c->stream));
-    HIPCHK(hipMemsetAsync(g->L - PRF_FRONT_PAD, 0, PRF_FRONT_PAD * 8, c->stream));
-    HIPCHK(hipMemsetAsync(g->X - PRF_FRONT_PAD, 0xFF, PRF_FRONT_PAD * 8, c->stream));
+    int rc = alloc_plane(c, g, &g->H, 0);
+    if (!rc) rc = alloc_plane(c, g, &g->L, 0);
+    if (!rc) rc = alloc_plane(c, g, &g->X, 0xFF);
+    if (rc) return rc;
     HIPCHK(hipMemsetAsync(c->d_counters, 0xFF, PRF_CNT_N * sizeof(u64), c->stream));
     HIPCHK(hipMemsetAsync(c->d_counters + PRF_CNT_EXOTIC, 0, sizeof(u64), c->stream));
     HIPCHK(prf_launch_pack_linear(c->stream, asc, g->nwords, g->H, g->L, g->X, c->d_counters + PRF_CNT_BADPOS,
                                   c->d_counters + PRF_CNT_EXOTIC));
-    HIPCHK(hipMemsetAsync(g->H + g->nwords, 0, g->padw * 8, c->stream));
-    HIPCHK(hipMemsetAsync(g->L + g->nwords, 0, g->padw * 8, c->stream));
-    HIPCHK(hipMemsetAsync(g->X + g->nwords, 0xFF, g->padw * 8, c->stream));
     HIPCHK(hipMalloc((void **)&g->d_base, sizeof(u64) * (size_t)(n_contigs > 0 ? n_contigs : 1)));
     if (n_contigs > 0)
         HIPCHK(hipMemcpyAsync(g->d_base, g->base.data(), sizeof(u64) * (size_t)n_contigs, hipMemcpyHostToDevice, c->stream));
-    {   // the contig of every tile (contigs start on tile boundaries; the gap tiles behind a contig count as its own)
-        const u64 ntiles = g->G / PRF_TILE;
-        std::vector<uint4> info(ntiles, make_uint4(0, 0, 0, 0));
-        for (size_t ci = 0; ci < g->base.size(); ci++) {
-            const u64 t0 = g->base[ci] / PRF_TILE, t1 = ci + 1 < g->base.size() ? g->base[ci + 1] / PRF_TILE : ntiles;
-            for (u64 t = t0; t < t1; t++) info[t] = make_uint4((u32)ci, 0u, (u32)g->base[ci], (u32)(g->base[ci] >> 32));
-        }
-        HIPCHK(hipMalloc((void **)&g->d_tile_info, sizeof(uint4) * ntiles));
-        HIPCHK(hipMemcpy(g->d_tile_info, info.data(), sizeof(uint4) * ntiles, hipMemcpyHostToDevice));
-    }
+    if ((rc = upload_tile_info(g))) return rc;
     // bit-sliced copy for the vertical kernel (built from the ASCII while it is still resident)
-    {
-        int rc = prf_vertical_pack(c->stream, asc, g->G, &g->vp);
-        if (rc != hipSuccess) return fail(rc == (int)hipErrorOutOfMemory ? PRF_ENOMEM : PRF_EHIP, "vertical pack failed: %s",
-                                          hipGetErrorString((hipError_t)rc));
-    }
+    rc = prf_vertical_pack(c->stream, asc, g->G, &g->vp);
+    if (rc != hipSuccess)
+        return fail(rc == (int)hipErrorOutOfMemory ? PRF_ENOMEM : PRF_EHIP, "vertical pack failed: %s", hipGetErrorString((hipError_t)rc));
     HIPCHK(hipMemcpyAsync(c->h_counters, c->d_counters, PRF_CNT_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     const u64 bad = c->h_counters[PRF_CNT_BADPOS];
@@ -346,76 +377,44 @@ static int genome_load_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs
                     "symbols, like the reference -- any other letter, in either case); libprf refuses other bytes instead of guessing",
                     ci, (unsigned long long)(bad - g->base[ci]));
     }
-    if (c->h_counters[PRF_CNT_EXOTIC]) {
-        // letters other than A, C, G, T, N: the planes of their codes, and the tile ranges the generic kernels take
-        for (int i = 0; i < 5; i++) {
-            u64 *p = nullptr;
-            HIPCHK(hipMalloc((void **)&p, tot * 8));
-            g->E[i] = p + PRF_FRONT_PAD;
-            HIPCHK(hipMemsetAsync(p, 0, PRF_FRONT_PAD * 8, c->stream));
-            HIPCHK(hipMemsetAsync(g->E[i] + g->nwords, 0, g->padw * 8, c->stream));
-        }
-        HIPCHK(prf_launch_pack_exotic(c->stream, asc, g->nwords, g->E));
-        HIPCHK(hipMalloc((void **)&g->d_E, 5 * sizeof(u64 *)));
-        HIPCHK(hipMemcpyAsync(g->d_E, g->E, 5 * sizeof(u64 *), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        const std::vector<unsigned char> &cls = g->vp.h_class;
-        for (u64 t = 0; t + 1 < cls.size(); t++) {
-            if (cls[t] != 3) continue;
-            if (!g->exotic_tiles.empty() && g->exotic_tiles.back().second == t) g->exotic_tiles.back().second = t + 1;
-            else g->exotic_tiles.emplace_back(t, t + 1);
-        }
-    }
+    if (c->h_counters[PRF_CNT_EXOTIC] && (rc = load_exotic(c, g, asc))) return rc;
     guard.g = nullptr;
     *out = g;
     return PRF_OK;
 }
 
 int prf_genome_load(prf_ctx *c, const prf_contig *contigs, int n_contigs, uint32_t kmax_hint, prf_genome **out) {
-    try {
-        return genome_load_impl(c, contigs, n_contigs, kmax_hint, out);
-    } catch (const std::bad_alloc &) {
-        return fail(PRF_ENOMEM, "prf_genome_load: out of host memory");
-    } catch (...) {
-        return fail(PRF_EHIP, "prf_genome_load: unexpected exception");
-    }
+    return guarded("prf_genome_load", [&] { return genome_load_impl(c, contigs, n_contigs, kmax_hint, out); });
+}
+
+// contigs generated on the device from seeds (recipe 1: uniform background, 2: stand-in recipe 2)
+static int genome_generate(const char *name, prf_ctx *c, const uint64_t *lens, const uint64_t *seeds, int n_contigs,
+                           uint32_t kmax_hint, prf_genome **out, int recipe) {
+    if (n_contigs < 0 || (n_contigs > 0 && (!lens || !seeds))) return fail(PRF_EINVAL, "%s: bad arguments", name);
+    return guarded(name, [&] {
+        std::vector<prf_contig> cs((size_t)(n_contigs > 0 ? n_contigs : 1));
+        for (int i = 0; i < n_contigs; i++) cs[i] = prf_contig{nullptr, lens[i]};
+        return genome_load_impl(c, cs.data(), n_contigs, kmax_hint, out, seeds, recipe);
+    });
 }
 
 int prf_genome_synth(prf_ctx *c, const uint64_t *lens, const uint64_t *seeds, int n_contigs, uint32_t kmax_hint, prf_genome **out) {
-    if (n_contigs < 0 || (n_contigs > 0 && (!lens || !seeds))) return fail(PRF_EINVAL, "prf_genome_synth: bad arguments");
-    try {
-        std::vector<prf_contig> cs((size_t)(n_contigs > 0 ? n_contigs : 1));
-        for (int i = 0; i < n_contigs; i++) cs[i] = prf_contig{nullptr, lens[i]};
-        return genome_load_impl(c, cs.data(), n_contigs, kmax_hint, out, seeds);
-    } catch (const std::bad_alloc &) {
-        return fail(PRF_ENOMEM, "prf_genome_synth: out of host memory");
-    } catch (...) {
-        return fail(PRF_EHIP, "prf_genome_synth: unexpected exception");
-    }
+    return genome_generate("prf_genome_synth", c, lens, seeds, n_contigs, kmax_hint, out, 1);
 }
 
 int prf_genome_standin(prf_ctx *c, const uint64_t *lens, const uint64_t *seeds, int n_contigs, uint32_t kmax_hint, prf_genome **out) {
-    if (n_contigs < 0 || (n_contigs > 0 && (!lens || !seeds))) return fail(PRF_EINVAL, "prf_genome_standin: bad arguments");
-    try {
-        std::vector<prf_contig> cs((size_t)(n_contigs > 0 ? n_contigs : 1));
-        for (int i = 0; i < n_contigs; i++) cs[i] = prf_contig{nullptr, lens[i]};
-        return genome_load_impl(c, cs.data(), n_contigs, kmax_hint, out, seeds, 2);
-    } catch (const std::bad_alloc &) {
-        return fail(PRF_ENOMEM, "prf_genome_standin: out of host memory");
-    } catch (...) {
-        return fail(PRF_EHIP, "prf_genome_standin: unexpected exception");
-    }
+    return genome_generate("prf_genome_standin", c, lens, seeds, n_contigs, kmax_hint, out, 2);
 }
+
+// words of d_block_sum for nslots launch slots: per 8 slots, then two words per PRF_GATHER_SUPER gather workgroups
+static size_t block_sum_words(u64 nslots) { return (size_t)(nslots / 8 + 1) + 2 * (size_t)(nslots / (8 * PRF_GATHER_SUPER) + 2); }
 
 // After a fused launch failed or never posted its counters the device-side counter blocks are in an unknown state
 // (the kernel clears the NEXT scan's block only when its last workgroup gets there): drain the stream, clear both.
 static void reset_vcounters(prf_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     (void)hipMemsetAsync(c->d_vcounters, 0, 2 * PRF_CNT_N * sizeof(u64), c->stream);
-    if (c->d_block_sum)
-        (void)hipMemsetAsync(c->d_block_sum, 0,
-                             ((size_t)(c->slab_slots / 8 + 1) + 2 * (size_t)(c->slab_slots / (8 * PRF_GATHER_SUPER) + 2)) * sizeof(u32),
-                             c->stream);
+    if (c->d_block_sum) (void)hipMemsetAsync(c->d_block_sum, 0, block_sum_words(c->slab_slots) * sizeof(u32), c->stream);
     (void)hipStreamSynchronize(c->stream);
 }
 
@@ -456,19 +455,20 @@ static int wait_for_seq(prf_ctx *c, u64 seq, const u64 *block = nullptr) {
     }
 }
 
+// the timing events of fused scan `seq`: before the scan kernel, between the two kernels, after the gather
+static hipEvent_t *ring_events(prf_ctx *c, u64 seq) { return &c->ring[3 * (seq % PRF_TIMING_RING)]; }
+
 static int scan_timings_impl(prf_ctx *c, uint64_t first_seq, uint32_t n, float *total_ms, float *scan_ms, float *gather_ms) {
     if (!c || first_seq == 0 || first_seq + n - 1 > c->scan_seq || c->scan_seq - first_seq >= PRF_TIMING_RING)
         return fail(PRF_EINVAL, "prf_scan_timings: scans %llu..%llu are not among the last %d fused scans of this context",
                     (unsigned long long)first_seq, (unsigned long long)(first_seq + n - 1), PRF_TIMING_RING);
     HIPCHK(hipSetDevice(c->dev));
     for (uint32_t i = 0; i < n; i++) {
-        const u64 q = first_seq + i;
-        hipEvent_t ev_a = c->ring[3 * (q % PRF_TIMING_RING)], ev_m = c->ring[3 * (q % PRF_TIMING_RING) + 1],
-                   ev_b = c->ring[3 * (q % PRF_TIMING_RING) + 2];
-        HIPCHK(hipEventSynchronize(ev_b));
-        if (total_ms) HIPCHK(hipEventElapsedTime(&total_ms[i], ev_a, ev_b));
-        if (scan_ms) HIPCHK(hipEventElapsedTime(&scan_ms[i], ev_a, ev_m));
-        if (gather_ms) HIPCHK(hipEventElapsedTime(&gather_ms[i], ev_m, ev_b));
+        const hipEvent_t *ev = ring_events(c, first_seq + i);
+        HIPCHK(hipEventSynchronize(ev[2]));
+        if (total_ms) HIPCHK(hipEventElapsedTime(&total_ms[i], ev[0], ev[2]));
+        if (scan_ms) HIPCHK(hipEventElapsedTime(&scan_ms[i], ev[0], ev[1]));
+        if (gather_ms) HIPCHK(hipEventElapsedTime(&gather_ms[i], ev[1], ev[2]));
     }
     return PRF_OK;
 }
@@ -484,47 +484,27 @@ int prf_scan_timings_split(prf_ctx *c, uint64_t first_seq, uint32_t n, float *sc
 }
 
 static int ensure_buffers(prf_ctx *c, u64 want_cand, u64 want_hits) {
-    if (want_cand > c->cand_cap) {
-        (void)hipFree(c->d_cand);
-        c->d_cand = nullptr;
-        c->cand_cap = 0;
-        HIPCHK(hipMalloc((void **)&c->d_cand, want_cand * sizeof(u64)));
-        c->cand_cap = want_cand;
-    }
-    if (want_hits > c->hit_cap) {
-        (void)hipFree(c->d_hits);
-        c->d_hits = nullptr;
-        c->hit_cap = 0;
-        HIPCHK(hipMalloc((void **)&c->d_hits, want_hits * sizeof(prf_hit_dev)));
-        c->hit_cap = want_hits;
-    }
-    return PRF_OK;
+    const int rc = grow(c->d_cand, c->cand_cap, want_cand);
+    return rc ? rc : grow(c->d_hits, c->hit_cap, want_hits);
 }
 
 static int ensure_slabs(prf_ctx *c, u64 nslots, u32 cap) {
-    if (nslots > c->slab_slots || cap > c->slab_cap) {
-        nslots = std::max<u64>(nslots, c->slab_slots);
-        cap = std::max<u32>(cap, c->slab_cap);
-        HIPCHK(hipStreamSynchronize(c->stream));  // no scan in flight may still use the old buffers
-        (void)hipFree(c->d_slabs);
-        (void)hipFree(c->d_long_ends);
-        (void)hipFree(c->d_slab_count);
-        (void)hipFree(c->d_block_sum);
-        c->d_slabs = nullptr;
-        c->d_long_ends = nullptr;
-        c->d_slab_count = nullptr;
-        c->d_block_sum = nullptr;
-        c->slab_slots = 0;
-        c->slab_cap = 0;
-        const size_t n_blocks = (size_t)(nslots / 8 + 1) + 2 * (size_t)(nslots / (8 * PRF_GATHER_SUPER) + 2);
-        HIPCHK(hipMalloc((void **)&c->d_slabs, nslots * (u64)cap * sizeof(u64)));
-        HIPCHK(hipMalloc((void **)&c->d_long_ends, nslots * (u64)PRF_LONG_PER_TILE * sizeof(u64)));
-        HIPCHK(hipMalloc((void **)&c->d_slab_count, nslots * sizeof(u32)));
-        HIPCHK(hipMalloc((void **)&c->d_block_sum, n_blocks * sizeof(u32)));
-        HIPCHK(hipMemset(c->d_block_sum, 0, n_blocks * sizeof(u32)));
-        c->slab_slots = nslots;
-        c->slab_cap = cap;
-    }
+    if (nslots <= c->slab_slots && cap <= c->slab_cap) return PRF_OK;
+    nslots = std::max<u64>(nslots, c->slab_slots);
+    cap = std::max<u32>(cap, c->slab_cap);
+    HIPCHK(hipStreamSynchronize(c->stream));  // no scan in flight may still use the old buffers
+    for (void *p : {(void *)c->d_slabs, (void *)c->d_long_ends, (void *)c->d_slab_count, (void *)c->d_block_sum}) (void)hipFree(p);
+    c->d_slabs = c->d_long_ends = nullptr;
+    c->d_slab_count = c->d_block_sum = nullptr;
+    c->slab_slots = c->slab_cap = 0;
+    const size_t n_blocks = block_sum_words(nslots);
+    HIPCHK(hipMalloc((void **)&c->d_slabs, nslots * (u64)cap * sizeof(u64)));
+    HIPCHK(hipMalloc((void **)&c->d_long_ends, nslots * (u64)PRF_LONG_PER_TILE * sizeof(u64)));
+    HIPCHK(hipMalloc((void **)&c->d_slab_count, nslots * sizeof(u32)));
+    HIPCHK(hipMalloc((void **)&c->d_block_sum, n_blocks * sizeof(u32)));
+    HIPCHK(hipMemset(c->d_block_sum, 0, n_blocks * sizeof(u32)));
+    c->slab_slots = nslots;
+    c->slab_cap = cap;
     return PRF_OK;
 }
 
@@ -541,19 +521,21 @@ static int launch_fused(prf_ctx *c, const prf_genome *g, const prf_vplan &plan, 
     a.slabs = c->d_slabs; a.long_ends = c->d_long_ends; a.slab_count = c->d_slab_count; a.block_sum = c->d_block_sum; a.slab_cap = c->slab_cap;
     // the gather takes 8 launch slots per workgroup on small launches (more workgroups in flight), 64 on large ones
     a.gather_shift = lv.n <= 8192u ? 3u : 5u;
-    {   // PRF_GATHER_SHIFT (diagnostic): launch slots per gather workgroup = 1 << shift, 3 .. 6
+#ifdef PRF_DIAG
+    {   // PRF_GATHER_SHIFT: launch slots per gather workgroup = 1 << shift, 3 .. 6
         static const int gs_env = getenv("PRF_GATHER_SHIFT") ? atoi(getenv("PRF_GATHER_SHIFT")) : -1;
         if (gs_env >= 3 && gs_env <= 6) a.gather_shift = (u32)gs_env;
     }
+    {   // PRF_SKIP: phases left out to time the others (wrong rows, timing only)
+        static const u32 skip_env = getenv("PRF_SKIP") ? (u32)strtoul(getenv("PRF_SKIP"), nullptr, 0) : 0u;
+        a.skip = skip_env;
+    }
+#endif
     a.super_off = (lv.n + (1u << a.gather_shift) - 1u) >> a.gather_shift;  // the gather's grid
     a.min_repeats = min_repeats; a.min_span = min_span;
     a.tile_info = g->d_tile_info;
     a.counters = c->d_vcounters + (size_t)c->parity * PRF_CNT_N;
     a.dbg = nullptr;
-    {
-        static const u32 skip_env = getenv("PRF_SKIP") ? (u32)strtoul(getenv("PRF_SKIP"), nullptr, 0) : 0u;  // diagnostic: wrong rows, timing only
-        a.skip = skip_env;
-    }
 #ifdef PRF_STAMPS
     {
         static u64 *dbg_buf = nullptr;
@@ -579,17 +561,16 @@ static int launch_fused(prf_ctx *c, const prf_genome *g, const prf_vplan &plan, 
     ga.seq = ++c->scan_seq;
     ga.next_counters = c->d_vcounters + (size_t)(c->parity ^ 1u) * PRF_CNT_N;
     c->parity ^= 1u;
-    hipEvent_t ev_a = c->ring[3 * (ga.seq % PRF_TIMING_RING)], ev_m = c->ring[3 * (ga.seq % PRF_TIMING_RING) + 1],
-               ev_b = c->ring[3 * (ga.seq % PRF_TIMING_RING) + 2];
-    HIPCHK(hipEventRecord(ev_a, c->stream));
+    const hipEvent_t *ev = ring_events(c, ga.seq);
+    HIPCHK(hipEventRecord(ev[0], c->stream));
     hipError_t le = prf_vertical_launch(c->stream, a);
-    if (le == hipSuccess) le = hipEventRecord(ev_m, c->stream);
+    if (le == hipSuccess) le = hipEventRecord(ev[1], c->stream);
     if (le == hipSuccess) le = prf_vertical_gather(c->stream, ga);
     if (le != hipSuccess) {
         reset_vcounters(c);
         return fail(PRF_EHIP, "fused scan launch failed: %s", hipGetErrorString(le));
     }
-    HIPCHK(hipEventRecord(ev_b, c->stream));
+    HIPCHK(hipEventRecord(ev[2], c->stream));
     *seq_out = ga.seq;
     return PRF_OK;
 }
@@ -597,251 +578,285 @@ static int launch_fused(prf_ctx *c, const prf_genome *g, const prf_vplan &plan, 
 static int literal_genome(prf_ctx *c, const prf_genome *g, u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_hits *out,
                           prf_scan_stats *stats);
 
-static int scan_impl(prf_ctx *c, const prf_genome *g, uint32_t kmin, uint32_t kmax, uint32_t min_repeats,
-                     uint32_t min_span, uint32_t flags, prf_hits *out, prf_scan_stats *stats) {
-    if (!c || !g) return fail(PRF_EINVAL, "prf_scan_genome: NULL context or genome");
-    if (g->ctx != c) return fail(PRF_EINVAL, "prf_scan_genome: genome belongs to another context");
-    if (out) { out->rows = nullptr; out->n = 0; }
-    // same conditions, same wording as the reference's ValueErrors (perfect_repeat_finder.py:23-30)
+// Same conditions, same wording as the reference's ValueErrors (perfect_repeat_finder.py:23-30), then the library's limits:
+// the motif sizes a resident genome was packed for (kmax_hint), or the literal lane's 60000 (kmax_hint 0).
+static int check_params(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, u32 kmax_hint) {
     if (kmin < 1) return fail(PRF_EINVAL, "min_motif_size is set to %u. It must be at least 1.", kmin);
     if (kmax < kmin) return fail(PRF_EINVAL, "max_motif_size is set to %u. It must be at least min_motif_size.", kmax);
     if (min_repeats < 1) return fail(PRF_EINVAL, "min_repeats is set to %u. It must be at least 1.", min_repeats);
     if (min_span < 1) return fail(PRF_EINVAL, "min_span is set to %u. It must be at least 1.", min_span);
     if (min_repeats > 1000000u || min_span > (1u << 30)) return fail(PRF_EINVAL, "threshold out of range");
-    if (min_repeats < 2) {  // outside the closed form of the packed kernels: the literal lane on the bytes rebuilt from the planes
-        HIPCHK(hipSetDevice(c->dev));
-        return literal_genome(c, g, kmin, kmax, min_repeats, min_span, out, stats);
-    }
-    if (kmax > g->kmax_hint)
-        return fail(PRF_EUNSUPPORTED, "max_motif_size %u exceeds the kmax_hint %u this genome was packed with", kmax,
-                    g->kmax_hint);
-    if (min_repeats > 1000000u || min_span > (1u << 30)) return fail(PRF_EINVAL, "threshold out of range");
-    HIPCHK(hipSetDevice(c->dev));
+    if (kmax_hint && kmax > kmax_hint)
+        return fail(PRF_EUNSUPPORTED, "max_motif_size %u exceeds the kmax_hint %u this genome was packed with", kmax, kmax_hint);
+    if (kmax > 60000) return fail(PRF_EUNSUPPORTED, "max_motif_size %u > 60000", kmax);
+    return PRF_OK;
+}
 
-    prf_planes pl{g->H, g->L, g->X, {g->E[0], g->E[1], g->E[2], g->E[3], g->E[4]}};
-    prf_vplan plan;
-    bool vs = !(flags & PRF_SCAN_FORCE_GENERIC) && prf_vertical_plan(kmin, kmax, min_repeats, min_span, &plan);
-    const launch_view lv = active_launch(g);
-    u64 want_cand = std::max<u64>(c->cand_cap, lv.positions / 8 + 65536);
-    u64 want_hits = std::max<u64>(c->hit_cap, lv.positions / 32 + 65536);
-    // rows per tile the slabs hold (8 bytes each): the densest 65536-position tile of the reference's golden chr22 BED has 748
-    // rows at motif sizes 1-6; a tile beyond the capacity grows the slabs and scans again
-    u32 slab_cap = std::max<u32>(c->slab_cap, 1024u);
-    float ms01 = 0, ms12 = 0;
+struct scan_params {
+    u32 kmin, kmax, min_repeats, min_span;
+};
+
+using tile_ranges = std::vector<std::pair<u64, u64>>;  // [first, last) tile ranges, ascending
+
+// where the rows of a scan go: the caller's row sink, or the context's own array
+struct row_dest {
+    prf_hit_dev *rows;
+    u64 cap;
+    bool is_sink;
+};
+static row_dest row_destination(const prf_ctx *c) {
+    return c->sink ? row_dest{c->sink, c->sink_cap, true} : row_dest{c->d_hits, c->hit_cap, false};
+}
+
+// the buffer sizes a scan asks for; a pass that overflowed raises them and the scan runs again
+struct buffer_sizes {
+    u64 cand, hits;
+    u32 slab_cap;
+};
+
+// what the passes of one scan attempt found
+struct pass_result {
     u64 ncand = 0, nhits = 0;
     u32 launches = 0;
-    bool sorted_on_device = false;
-    for (int attempt = 0;; attempt++) {
-        if (attempt > 8) return fail(PRF_EHIP, "prf_scan_genome: buffers still overflowing after 8 attempts");
-        bool again = false;
-        if (vs) {
-            // ---- fused bit-sliced kernel (scan + verify + sorted rows per tile), then the row gather ----
-            // tiles with a symbol outside ACGTN in reach are not on the launch list: the generic kernels take them below
-            std::vector<std::pair<u64, u64>> exotic;
-            if (!g->exotic_tiles.empty()) {
-                if (!g->sel_on) exotic = g->exotic_tiles;
-                else
-                    for (const auto &e : g->exotic_tiles)
-                        for (const auto &r : g->sel_tiles) {
-                            const u64 lo = std::max(e.first, r.first), hi = std::min(e.second, r.second);
-                            if (lo < hi) exotic.emplace_back(lo, hi);
-                        }
-            }
-            if (lv.n == 0 && exotic.empty()) {  // nothing but N (or no contig at all): no tile to launch, no rows
-                nhits = ncand = 0;
-                launches = 0;
-                sorted_on_device = true;
-                if (c->sink) {
-                    HIPCHK(hipMemsetAsync(c->sink + c->sink_cap, 0, sizeof(prf_hit_dev), c->stream));
-                    HIPCHK(hipStreamSynchronize(c->stream));
-                }
-                break;
-            }
-            if (lv.n == 0) {  // only such tiles: no fused launch
-                int rc0 = ensure_buffers(c, want_cand, want_hits);
-                if (rc0) return rc0;
-                nhits = ncand = 0;
-                launches = 0;
-                sorted_on_device = true;
-            } else {
-            int rc = ensure_slabs(c, lv.n, slab_cap);
-            if (rc) return rc;
-            rc = ensure_buffers(c, c->cand_cap, want_hits);  // the compact row array
-            if (rc) return rc;
-            u64 seq = 0;
-            rc = launch_fused(c, g, plan, min_repeats, min_span, c->sink ? c->sink : c->d_hits, c->sink ? c->sink_cap : c->hit_cap,
-                              c->sink ? 1u : 0u, c->h_counters_dev, &seq);
-            if (rc) return rc;
-            hipEvent_t ev_a = c->ring[3 * (seq % PRF_TIMING_RING)], ev_b = c->ring[3 * (seq % PRF_TIMING_RING) + 2];
-            // The scan is over for the host when the gather's last workgroup has posted the counter block and this
-            // scan's serial number in mapped host memory: poll that word instead of waiting for the stream to drain
-            // (the kernel's end-of-grid handshake, the event and the wake-up cost ~5 us).
-            // Everything that consumes the rows is enqueued on the same stream, hence ordered after the kernels.
-            rc = wait_for_seq(c, seq);
-            if (rc) return rc;
+    bool sorted = true;  // the rows are sorted by (contig, start, end) on the device
+    float ms01 = 0, ms12 = 0;
+    bool again = false;  // a buffer was too small (buffer_sizes raised): scan again
+};
+
+// The count record {n, 0, 0} behind a caller-owned row array (dst[cap]), staged in the spare pinned words behind the counter
+// block.  Returns when it is on the device.
+static int write_count_record(prf_ctx *c, prf_hit_dev *dst, u64 cap, u64 n) {
+    u64 *stage = c->h_counters + PRF_CNT_N + 2;
+    stage[0] = n; stage[1] = 0; stage[2] = 0;
+    HIPCHK(hipMemcpyAsync(dst + cap, stage, sizeof(prf_hit_dev), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return PRF_OK;
+}
+
+static int sink_too_small(const prf_ctx *c, u64 nhits) {
+    return fail(PRF_EINVAL, "the row sink holds %llu rows, the scan found %llu", (unsigned long long)c->sink_cap,
+                (unsigned long long)nhits);
+}
+
+// one word (PRF_SH_CAND, PRF_SH_EARLY) summed over the shards of a fused scan's counter block
+static u64 shard_sum(const u64 *h, int word) {
+    u64 s = 0;
+    for (int sh = 0; sh < PRF_CNT_NSHARD; sh++) s += h[PRF_CNT_SHARD0 + sh * PRF_CNT_SHARD_STRIDE + word];
+    return s;
+}
+
+// what a fused scan (one scan kernel + one gather) posted in its host counter block
+static pass_result read_fused(const u64 *h) {
+    pass_result r;
+    r.nhits = h[PRF_CNT_ROWS];
+    r.sorted = h[PRF_CNT_UNSORTED] == 0;
+    r.ncand = shard_sum(h, PRF_SH_CAND);
+    r.launches = 2;
+    return r;
+}
+
+static void fill_stats(prf_scan_stats *s, const pass_result &r, u32 path, u64 positions, u32 tiles, u64 seq) {
+    memset(s, 0, sizeof *s);
+    s->phase1_ms = r.ms01;
+    s->phase2_ms = r.ms12;
+    s->scan_ms = (double)r.ms01 + (double)r.ms12;
+    s->positions = positions;
+    s->packed_bytes = (positions + 3) / 4;
+    s->n_candidates = r.ncand;
+    s->n_hits = r.nhits;
+    s->n_launches = r.launches;
+    s->path = path;
+    s->seq = seq;
+    s->sorted_on_device = r.sorted ? 1u : 0u;
+    s->tiles_launched = tiles;
+}
+
 #ifdef PRF_STAMPS
-            if (const char *path = getenv("PRF_STAMPS_OUT")) {
-                fprintf(stderr, "[prf] plan: %u waves, %u tasks\n", plan.n_waves, plan.n_tasks);
-                for (u32 w = 0; w < plan.n_waves; w++)
-                    for (u32 ti = plan.wave_begin[w]; ti < plan.wave_begin[w + 1]; ti++)
-                        fprintf(stderr, "[prf]   wave %u slot %u: kind %u k0 %u valid %02x stride %u\n", w, ti - plan.wave_begin[w],
-                                plan.tasks[ti].kind, plan.tasks[ti].k0, plan.tasks[ti].valid, plan.tasks[ti].stride);
-                if (c->stamps_buf) {
-                    HIPCHK(hipStreamSynchronize(c->stream));
-                    const size_t nu = (size_t)c->stamps_n * PRF_VMAX_WAVES * 16;
-                    std::vector<u64> host(nu);
-                    HIPCHK(hipMemcpy(host.data(), c->stamps_buf, nu * sizeof(u64), hipMemcpyDeviceToHost));
-                    if (FILE *f = fopen(path, "wb")) { fwrite(host.data(), 8, nu, f); fclose(f); }
-                }
-            }
+static int dump_stamps(prf_ctx *c, const prf_vplan &plan) {
+    const char *path = getenv("PRF_STAMPS_OUT");
+    if (!path) return PRF_OK;
+    fprintf(stderr, "[prf] plan: %u waves, %u tasks\n", plan.n_waves, plan.n_tasks);
+    for (u32 w = 0; w < plan.n_waves; w++)
+        for (u32 ti = plan.wave_begin[w]; ti < plan.wave_begin[w + 1]; ti++)
+            fprintf(stderr, "[prf]   wave %u slot %u: kind %u k0 %u valid %02x stride %u\n", w, ti - plan.wave_begin[w],
+                    plan.tasks[ti].kind, plan.tasks[ti].k0, plan.tasks[ti].valid, plan.tasks[ti].stride);
+    if (c->stamps_buf) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        const size_t nu = (size_t)c->stamps_n * PRF_VMAX_WAVES * 16;
+        std::vector<u64> host(nu);
+        HIPCHK(hipMemcpy(host.data(), c->stamps_buf, nu * sizeof(u64), hipMemcpyDeviceToHost));
+        if (FILE *f = fopen(path, "wb")) { fwrite(host.data(), 8, nu, f); fclose(f); }
+    }
+    return PRF_OK;
+}
 #endif
-            // a row sink is read by the caller on streams of its own: wait until every workgroup has copied its rows
-            if (c->sink) HIPCHK(hipStreamSynchronize(c->stream));
-            if (stats && !(flags & PRF_SCAN_DEFER_TIMING)) {
-                HIPCHK(hipEventSynchronize(ev_b));
-                HIPCHK(hipEventElapsedTime(&ms01, ev_a, ev_b));
-            }
-            ms12 = 0;
-            launches = 2u * (u32)(attempt + 1);  // (a scan that had to grow its buffers and run again shows here)
-            nhits = c->h_counters[PRF_CNT_ROWS];
-            sorted_on_device = c->h_counters[PRF_CNT_UNSORTED] == 0;
-            ncand = 0;
-            for (int sh = 0; sh < PRF_CNT_NSHARD; sh++)
-                ncand += c->h_counters[PRF_CNT_SHARD0 + sh * PRF_CNT_SHARD_STRIDE + PRF_SH_CAND];
-            if (getenv("PRF_DEBUG")) {
-                u64 nearly = 0;
-                for (int sh = 0; sh < PRF_CNT_NSHARD; sh++) nearly += c->h_counters[PRF_CNT_SHARD0 + sh * PRF_CNT_SHARD_STRIDE + PRF_SH_EARLY];
-                fprintf(stderr, "[prf] fused: hits %llu cand-records %llu (verified on the spot, a list being full: %llu) hit_ovf %llu unsorted %llu ms %.4f\n",
-                        (unsigned long long)nhits, (unsigned long long)ncand, (unsigned long long)nearly,
-                        (unsigned long long)c->h_counters[PRF_CNT_HIT_OVF], (unsigned long long)c->h_counters[PRF_CNT_UNSORTED], ms01);
-            }
-            if (c->h_counters[PRF_CNT_LONG_OVF])
-                return fail(PRF_EHIP, "internal: a tile reported %llu rows longer than 65534 positions (at most %u can exist)",
-                            (unsigned long long)c->h_counters[PRF_CNT_LONG_OVF], PRF_LONG_PER_TILE);
-            const u64 hit_ovf = c->h_counters[PRF_CNT_HIT_OVF];
-            if (hit_ovf > c->slab_cap) { slab_cap = (u32)std::min<u64>(hit_ovf + hit_ovf / 4 + 64, 1u << 22); again = true; }
-            if (!again && c->sink && nhits > c->sink_cap)
-                return fail(PRF_EINVAL, "the row sink holds %llu rows, the scan found %llu", (unsigned long long)c->sink_cap,
-                            (unsigned long long)nhits);
-            if (!again && !c->sink && nhits > c->hit_cap) {  // the compact row array was too small: grow it and scan again
-                want_hits = nhits + nhits / 8 + 1024;
-                again = true;
-            }
-            }  // fused launch
-            if (!again && !exotic.empty()) {
-                // ---- tiles with symbols outside ACGTN in reach: generic kernels with the symbols' own planes (R == R matches,
-                // reference utils/perfect_repeat_tracker.py:53); a row belongs to the tile of its first position there too, so
-                // the two row sets are disjoint.  The rows are appended; the array is then sorted on the host.
-                int rc = ensure_buffers(c, want_cand, c->hit_cap);
-                if (rc) return rc;
-                prf_hit_dev *rows_base = c->sink ? c->sink : c->d_hits;
-                const u64 rows_cap = c->sink ? c->sink_cap : c->hit_cap;
-                const u64 room = rows_cap > nhits ? rows_cap - nhits : 0;
-                HIPCHK(hipMemsetAsync(c->d_counters, 0, PRF_CNT_N * sizeof(u64), c->stream));
-                for (const auto &tr : exotic)
-                    HIPCHK(prf_launch_scan_generic(c->stream, pl, tr.first * PRF_TILE_WORDS, tr.second * PRF_TILE_WORDS, kmin, kmax,
-                                                   min_repeats, min_span, c->d_cand, c->cand_cap, c->d_counters));
-                HIPCHK(prf_launch_verify(c->stream, pl, c->d_cand, c->cand_cap, min_repeats, min_span, g->d_base, (u32)g->base.size(),
-                                         rows_base + nhits, room, c->d_counters));
-                u64 *stage = c->h_counters + PRF_CNT_N + 2;  // spare pinned words behind the counter block
-                HIPCHK(hipMemcpyAsync(stage, c->d_counters, 2 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipStreamSynchronize(c->stream));
-                const u64 ncand_g = stage[PRF_CNT_CAND], nhits_g = stage[PRF_CNT_HITS];
-                launches += 1 + (u32)exotic.size();
-                if (ncand_g > c->cand_cap) { want_cand = ncand_g + ncand_g / 8 + 1024; again = true; }
-                if (!again && nhits_g > room) {
-                    if (c->sink)
-                        return fail(PRF_EINVAL, "the row sink holds %llu rows, the scan found %llu", (unsigned long long)c->sink_cap,
-                                    (unsigned long long)(nhits + nhits_g));
-                    want_hits = nhits + nhits_g + (nhits + nhits_g) / 8 + 1024;
-                    again = true;
-                }
-                if (!again) {
-                    ncand += ncand_g;
-                    nhits += nhits_g;
-                    if (nhits_g) sorted_on_device = false;
-                    if (c->sink) {  // the count record behind a caller-owned row array
-                        stage[0] = nhits; stage[1] = 0; stage[2] = 0;
-                        HIPCHK(hipMemcpyAsync(c->sink + c->sink_cap, stage, sizeof(prf_hit_dev), hipMemcpyHostToDevice, c->stream));
-                        HIPCHK(hipStreamSynchronize(c->stream));
-                    }
-                }
-            }
-        } else {
-            // ---- generic path: candidates, then rows ----
-            int rc = ensure_buffers(c, want_cand, want_hits);
-            if (rc) return rc;
-            HIPCHK(hipMemsetAsync(c->d_counters, 0, PRF_CNT_N * sizeof(u64), c->stream));
-            HIPCHK(hipEventRecord(c->ev[0], c->stream));
-            // a run belongs to the word that holds its first position: disjoint word ranges give disjoint row sets
-            if (g->sel_on) {
-                for (const auto &tr : g->sel_tiles)
-                    HIPCHK(prf_launch_scan_generic(c->stream, pl, tr.first * PRF_TILE_WORDS, tr.second * PRF_TILE_WORDS, kmin, kmax,
-                                                   min_repeats, min_span, c->d_cand, c->cand_cap, c->d_counters));
-            } else {
-                HIPCHK(prf_launch_scan_generic(c->stream, pl, 0, g->nwords - PRF_TILE_WORDS, kmin, kmax, min_repeats, min_span,
-                                               c->d_cand, c->cand_cap, c->d_counters));
-            }
-            HIPCHK(hipEventRecord(c->ev[1], c->stream));
-            HIPCHK(prf_launch_verify(c->stream, pl, c->d_cand, c->cand_cap, min_repeats, min_span, g->d_base,
-                                     (u32)g->base.size(), c->d_hits, c->hit_cap, c->d_counters));
-            HIPCHK(hipEventRecord(c->ev[2], c->stream));
-            HIPCHK(hipMemcpyAsync(c->h_counters, c->d_counters, PRF_CNT_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            HIPCHK(hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]));
-            HIPCHK(hipEventElapsedTime(&ms12, c->ev[1], c->ev[2]));
-            launches = 2;
-            ncand = c->h_counters[PRF_CNT_CAND];
-            nhits = c->h_counters[PRF_CNT_HITS];
-            if (ncand > c->cand_cap) { want_cand = ncand + ncand / 8 + 1024; again = true; }
-            if (nhits > c->hit_cap) { want_hits = nhits + nhits / 8 + 1024; again = true; }
-            if (!again && c->sink) {  // the generic kernels write the internal array: hand the rows over afterwards
-                if (nhits > c->sink_cap)
-                    return fail(PRF_EINVAL, "the row sink holds %llu rows, the scan found %llu", (unsigned long long)c->sink_cap,
-                                (unsigned long long)nhits);
-                u64 *stage = c->h_counters + PRF_CNT_N + 2;
-                stage[0] = nhits; stage[1] = 0; stage[2] = 0;
-                if (nhits) HIPCHK(hipMemcpyAsync(c->sink, c->d_hits, nhits * sizeof(prf_hit_dev), hipMemcpyDeviceToDevice, c->stream));
-                HIPCHK(hipMemcpyAsync(c->sink + c->sink_cap, stage, sizeof(prf_hit_dev), hipMemcpyHostToDevice, c->stream));
-                HIPCHK(hipStreamSynchronize(c->stream));
-            }
+
+// ---- fused bit-sliced kernel (scan + verify + sorted rows per tile), then the row gather into dst ----
+// Tiles with a symbol outside ACGTN in reach are not on the launch list: exotic_pass takes them.
+static int fused_pass(prf_ctx *c, const prf_genome *g, const prf_vplan &plan, const scan_params &p, const row_dest &dst, bool timed,
+                      buffer_sizes *want, pass_result *r) {
+    u64 seq = 0;
+    int rc = launch_fused(c, g, plan, p.min_repeats, p.min_span, dst.rows, dst.cap, dst.is_sink ? 1u : 0u, c->h_counters_dev, &seq);
+    if (rc) return rc;
+    // The scan is over for the host when the gather's last workgroup has posted the counter block and this scan's serial
+    // number in mapped host memory: poll that word instead of waiting for the stream to drain (the kernel's end-of-grid
+    // handshake, the event and the wake-up cost ~5 us).  Everything that consumes the rows is enqueued on the same stream,
+    // hence ordered after the kernels.
+    rc = wait_for_seq(c, seq);
+    if (rc) return rc;
+#ifdef PRF_STAMPS
+    rc = dump_stamps(c, plan);
+    if (rc) return rc;
+#endif
+    // a row sink is read by the caller on streams of its own: wait until every workgroup has copied its rows
+    if (dst.is_sink) HIPCHK(hipStreamSynchronize(c->stream));
+    const u64 *h = c->h_counters;
+    *r = read_fused(h);
+    if (timed) {
+        const hipEvent_t *ev = ring_events(c, seq);
+        HIPCHK(hipEventSynchronize(ev[2]));
+        HIPCHK(hipEventElapsedTime(&r->ms01, ev[0], ev[2]));
+    }
+#ifdef PRF_DIAG
+    if (getenv("PRF_DEBUG"))
+        fprintf(stderr, "[prf] fused: hits %llu cand-records %llu (verified on the spot, a list being full: %llu) hit_ovf %llu unsorted %llu ms %.4f\n",
+                (unsigned long long)r->nhits, (unsigned long long)r->ncand, (unsigned long long)shard_sum(h, PRF_SH_EARLY),
+                (unsigned long long)h[PRF_CNT_HIT_OVF], (unsigned long long)h[PRF_CNT_UNSORTED], r->ms01);
+#endif
+    if (h[PRF_CNT_LONG_OVF])
+        return fail(PRF_EHIP, "internal: a tile reported %llu rows longer than 65534 positions (at most %u can exist)",
+                    (unsigned long long)h[PRF_CNT_LONG_OVF], PRF_LONG_PER_TILE);
+    const u64 hit_ovf = h[PRF_CNT_HIT_OVF];
+    if (hit_ovf > c->slab_cap) {  // a tile held more rows than its slab: grow the slabs
+        want->slab_cap = (u32)std::min<u64>(hit_ovf + hit_ovf / 4 + 64, 1u << 22);
+        r->again = true;
+    } else if (r->nhits > dst.cap) {  // the compact row array was too small
+        if (dst.is_sink) return sink_too_small(c, r->nhits);
+        want->hits = r->nhits + r->nhits / 8 + 1024;
+        r->again = true;
+    }
+    return PRF_OK;
+}
+
+// ---- generic kernels over tile ranges (candidates), then verify (rows to rows[0 .. room)) ----
+// A run belongs to the word that holds its first position: disjoint ranges give disjoint row sets.
+static int tiles_pass(prf_ctx *c, const prf_genome *g, const scan_params &p, const tile_ranges &tiles, prf_hit_dev *rows, u64 room,
+                      pass_result *r) {
+    const prf_planes pl{g->H, g->L, g->X, {g->E[0], g->E[1], g->E[2], g->E[3], g->E[4]}};
+    HIPCHK(hipMemsetAsync(c->d_counters, 0, PRF_CNT_N * sizeof(u64), c->stream));
+    HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    for (const auto &tr : tiles)
+        HIPCHK(prf_launch_scan_generic(c->stream, pl, tr.first * PRF_TILE_WORDS, tr.second * PRF_TILE_WORDS, p.kmin, p.kmax,
+                                       p.min_repeats, p.min_span, c->d_cand, c->cand_cap, c->d_counters));
+    HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    HIPCHK(prf_launch_verify(c->stream, pl, c->d_cand, c->cand_cap, p.min_repeats, p.min_span, g->d_base, (u32)g->base.size(), rows,
+                             room, c->d_counters));
+    HIPCHK(hipEventRecord(c->ev[2], c->stream));
+    u64 *stage = c->h_counters + PRF_CNT_N + 2;  // spare pinned words behind the counter block
+    HIPCHK(hipMemcpyAsync(stage, c->d_counters, 2 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    r->ncand = stage[PRF_CNT_CAND];
+    r->nhits = stage[PRF_CNT_HITS];
+    HIPCHK(hipEventElapsedTime(&r->ms01, c->ev[0], c->ev[1]));
+    HIPCHK(hipEventElapsedTime(&r->ms12, c->ev[1], c->ev[2]));
+    return PRF_OK;
+}
+
+// The tiles with a symbol outside ACGTN in reach (class 3), within the active selection if there is one
+static tile_ranges exotic_ranges(const prf_genome *g) {
+    if (!g->sel_on) return g->exotic_tiles;
+    tile_ranges out;
+    for (const auto &e : g->exotic_tiles)
+        for (const auto &r : g->sel_tiles) {
+            const u64 lo = std::max(e.first, r.first), hi = std::min(e.second, r.second);
+            if (lo < hi) out.emplace_back(lo, hi);
         }
-        if (!again) break;
+    return out;
+}
+
+// ---- fused path, second pass: the tiles with symbols outside ACGTN, on the generic kernels with the symbols' own planes
+// (R == R matches, reference utils/perfect_repeat_tracker.py:53).  A row belongs to the tile of its first position there too,
+// so the two row sets are disjoint.  The rows are appended behind the fused pass's; the array is then sorted on the host.
+static int exotic_pass(prf_ctx *c, const prf_genome *g, const scan_params &p, const tile_ranges &exotic, const row_dest &dst,
+                       buffer_sizes *want, pass_result *r) {
+    const u64 room = dst.cap > r->nhits ? dst.cap - r->nhits : 0;
+    pass_result e;
+    const int rc = tiles_pass(c, g, p, exotic, dst.rows + r->nhits, room, &e);
+    if (rc) return rc;
+    r->launches += 1 + (u32)exotic.size();
+    const u64 total = r->nhits + e.nhits;
+    if (e.ncand > c->cand_cap) {
+        want->cand = e.ncand + e.ncand / 8 + 1024;
+        r->again = true;
+    } else if (e.nhits > room) {
+        if (dst.is_sink) return sink_too_small(c, total);
+        want->hits = total + total / 8 + 1024;
+        r->again = true;
+    } else {
+        r->ncand += e.ncand;
+        r->nhits = total;
+        if (e.nhits) r->sorted = false;
+        if (dst.is_sink) return write_count_record(c, dst.rows, dst.cap, total);
     }
-    c->last_nhits = nhits;
-    c->last_kmax = kmax;
-    c->last_rows = c->sink ? c->sink : c->d_hits;
-    c->last_sorted = sorted_on_device;
-    if (stats) {
-        stats->phase1_ms = ms01;
-        stats->phase2_ms = ms12;
-        stats->scan_ms = (double)ms01 + (double)ms12;
-        stats->positions = lv.positions;
-        stats->packed_bytes = (lv.positions + 3) / 4;
-        stats->n_candidates = ncand;
-        stats->n_hits = nhits;
-        stats->n_launches = launches;
-        stats->path = vs ? 1 : 0;
-        stats->seq = vs && launches ? c->scan_seq : 0;
-        stats->sorted_on_device = sorted_on_device ? 1u : 0u;
-        stats->tiles_launched = vs ? lv.n : 0u;
+    return PRF_OK;
+}
+
+// ---- generic path: candidates, then rows, over the active selection or the whole genome (its sentinel tile aside) ----
+static int generic_pass(prf_ctx *c, const prf_genome *g, const scan_params &p, buffer_sizes *want, pass_result *r) {
+    const tile_ranges whole{{0, g->G / PRF_TILE - 1}};
+    const int rc = tiles_pass(c, g, p, g->sel_on ? g->sel_tiles : whole, c->d_hits, c->hit_cap, r);
+    if (rc) return rc;
+    r->launches = 2;
+    r->sorted = false;
+    if (r->ncand > c->cand_cap) { want->cand = r->ncand + r->ncand / 8 + 1024; r->again = true; }
+    if (r->nhits > c->hit_cap) { want->hits = r->nhits + r->nhits / 8 + 1024; r->again = true; }
+    if (r->again || !c->sink) return PRF_OK;
+    // the generic kernels write the context's array: the rows are handed to the sink afterwards
+    if (r->nhits > c->sink_cap) return sink_too_small(c, r->nhits);
+    if (r->nhits) HIPCHK(hipMemcpyAsync(c->sink, c->d_hits, r->nhits * sizeof(prf_hit_dev), hipMemcpyDeviceToDevice, c->stream));
+    return write_count_record(c, c->sink, c->sink_cap, r->nhits);
+}
+
+// The passes of a scan (plan: the fused plan, or nullptr for the generic path), repeated with larger buffers while one overflows
+static int run_passes(prf_ctx *c, const prf_genome *g, const scan_params &p, const prf_vplan *plan, const tile_ranges &exotic,
+                      bool timed, pass_result *r) {
+    const launch_view lv = active_launch(g);
+    const bool fused = plan && lv.n > 0;
+    // rows per tile the slabs hold (8 bytes each): the densest 65536-position tile of the reference's golden chr22 BED has 748
+    // rows at motif sizes 1-6
+    buffer_sizes want{std::max<u64>(c->cand_cap, lv.positions / 8 + 65536), std::max<u64>(c->hit_cap, lv.positions / 32 + 65536),
+                      std::max<u32>(c->slab_cap, 1024u)};
+    for (int attempt = 0; attempt <= 8; attempt++) {
+        int rc = fused ? ensure_slabs(c, lv.n, want.slab_cap) : PRF_OK;
+        if (!rc) rc = ensure_buffers(c, fused && exotic.empty() ? c->cand_cap : want.cand, want.hits);  // (d_cand: generic kernels only)
+        *r = pass_result{};
+        if (!rc && !plan) rc = generic_pass(c, g, p, &want, r);
+        if (!rc && fused) {
+            rc = fused_pass(c, g, *plan, p, row_destination(c), timed, &want, r);
+            r->launches = 2u * (attempt + 1);  // (a scan that had to grow its buffers and run again shows here)
+        }
+        if (!rc && plan && !r->again && !exotic.empty()) rc = exotic_pass(c, g, p, exotic, row_destination(c), &want, r);
+        if (rc || !r->again) return rc;
     }
-    if ((flags & PRF_SCAN_NO_FETCH) || !out) return PRF_OK;
-    if (nhits == 0) return PRF_OK;
+    return fail(PRF_EHIP, "prf_scan_genome: buffers still overflowing after 8 attempts");
+}
+
+// The rows of the last scan to the host.  The fused path hands them over sorted by (contig, start, end) (reference
+// perfect_repeat_finder.py:81); the generic path, and a fused scan in which some tile held more rows than its LDS sort list,
+// are sorted here.
+static int fetch_rows(prf_ctx *c, u64 nhits, bool sorted, prf_hits *out) {
     prf_hit *rows = (prf_hit *)malloc(nhits * sizeof(prf_hit));
     if (!rows) return fail(PRF_ENOMEM, "prf_scan_genome: cannot allocate %llu rows", (unsigned long long)nhits);
     static_assert(sizeof(prf_hit) == sizeof(prf_hit_dev), "row layouts must agree");
     // on the library's stream: the scan returned when the counters were posted, the last workgroups may still be
     // copying their rows, and the stream is a non-blocking one (the null stream does not wait for it)
-    hipError_t e = hipMemcpyAsync(rows, c->last_rows, nhits * sizeof(prf_hit), hipMemcpyDeviceToHost, c->stream);
+    hipError_t e = hipMemcpyAsync(rows, c->last.rows, nhits * sizeof(prf_hit), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         free(rows);
         return fail(PRF_EHIP, "row copy failed: %s", hipGetErrorString(e));
     }
-    // The fused path hands the rows over sorted by (contig, start, end) (reference perfect_repeat_finder.py:81).  The
-    // generic path, and a fused scan in which some tile held more rows than its LDS sort list, are sorted here.
-    if (!sorted_on_device)
+    if (!sorted)
         std::sort(rows, rows + nhits, [](const prf_hit &a, const prf_hit &b) {
             if (a.contig != b.contig) return a.contig < b.contig;
             if (a.start != b.start) return a.start < b.start;
@@ -853,15 +868,37 @@ static int scan_impl(prf_ctx *c, const prf_genome *g, uint32_t kmin, uint32_t km
     return PRF_OK;
 }
 
+static int scan_impl(prf_ctx *c, const prf_genome *g, uint32_t kmin, uint32_t kmax, uint32_t min_repeats,
+                     uint32_t min_span, uint32_t flags, prf_hits *out, prf_scan_stats *stats) {
+    if (!c || !g) return fail(PRF_EINVAL, "prf_scan_genome: NULL context or genome");
+    if (g->ctx != c) return fail(PRF_EINVAL, "prf_scan_genome: genome belongs to another context");
+    if (out) { out->rows = nullptr; out->n = 0; }
+    int rc = check_params(kmin, kmax, min_repeats, min_span, min_repeats < 2 ? 0u : g->kmax_hint);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->dev));
+    // outside the closed form of the packed kernels: the literal lane on the bytes rebuilt from the planes
+    if (min_repeats < 2) return literal_genome(c, g, kmin, kmax, min_repeats, min_span, out, stats);
+
+    prf_vplan plan;
+    const bool vs = !(flags & PRF_SCAN_FORCE_GENERIC) && prf_vertical_plan(kmin, kmax, min_repeats, min_span, &plan);
+    const launch_view lv = active_launch(g);
+    const tile_ranges exotic = vs ? exotic_ranges(g) : tile_ranges{};
+    pass_result r;
+    if (vs && lv.n == 0 && exotic.empty())  // nothing but N (or no contig at all): no tile to launch, no rows
+        rc = c->sink ? write_count_record(c, c->sink, c->sink_cap, 0) : PRF_OK;
+    else
+        rc = run_passes(c, g, scan_params{kmin, kmax, min_repeats, min_span}, vs ? &plan : nullptr, exotic,
+                        stats && !(flags & PRF_SCAN_DEFER_TIMING), &r);
+    if (rc) return rc;
+    c->last = {row_destination(c).rows, r.nhits, kmax};
+    if (stats) fill_stats(stats, r, vs ? 1u : 0u, lv.positions, vs ? lv.n : 0u, vs && r.launches ? c->scan_seq : 0);
+    if ((flags & PRF_SCAN_NO_FETCH) || !out || r.nhits == 0) return PRF_OK;
+    return fetch_rows(c, r.nhits, r.sorted, out);
+}
+
 int prf_scan_genome(prf_ctx *c, const prf_genome *g, uint32_t kmin, uint32_t kmax, uint32_t min_repeats,
                     uint32_t min_span, uint32_t flags, prf_hits *out, prf_scan_stats *stats) {
-    try {
-        return scan_impl(c, g, kmin, kmax, min_repeats, min_span, flags, out, stats);
-    } catch (const std::bad_alloc &) {
-        return fail(PRF_ENOMEM, "prf_scan_genome: out of host memory");
-    } catch (...) {
-        return fail(PRF_EHIP, "prf_scan_genome: unexpected exception");
-    }
+    return guarded("prf_scan_genome", [&] { return scan_impl(c, g, kmin, kmax, min_repeats, min_span, flags, out, stats); });
 }
 
 // ---- the literal lane (scan_literal.hip): regimes outside the closed form ----
@@ -877,8 +914,9 @@ struct dev_free {
 }  // namespace
 
 // d_seq: L bytes on the device (16-byte aligned: the 64-positions kernel reads whole 16-byte groups, 16 readable bytes behind them); upper: not upper-cased / validated yet
+// front: the N trimmed off the front of the contig -- the rows and the position of an unsupported symbol are shifted by it
 static int literal_device(prf_ctx *c, uint8_t *d_seq, u64 L, bool upper, u32 contig_index, u32 kmin, u32 kmax, u32 min_repeats,
-                          u32 min_span, u64 stop, std::vector<prf_hit> &rows_out, float *ms, u32 *launches, u64 pos_offset = 0) {
+                          u32 min_span, u64 stop, std::vector<prf_hit> &rows_out, float *ms, u32 *launches, u64 front) {
     if (stop > L) stop = L;
     dev_free rows;
     u64 cap = L / 16 + 4096;
@@ -902,13 +940,12 @@ static int literal_device(prf_ctx *c, uint8_t *d_seq, u64 L, bool upper, u32 con
             return fail(PRF_ESYMBOL,
                         "unsupported symbol at contig %u position %llu: only letters are accepted (A, C, G, T, N and -- as ordinary "
                         "symbols, like the reference -- any other letter, in either case); libprf refuses other bytes instead of guessing",
-                        contig_index, (unsigned long long)(h[PRF_CNT_BADPOS] + pos_offset));  // (pos_offset: the N trimmed off the front)
+                        contig_index, (unsigned long long)(h[PRF_CNT_BADPOS] + front));
         if (h[PRF_CNT_CAND])
             return fail(PRF_EINDEX, "string index out of range");  // the message of Python's IndexError (tracker :87)
         const u64 n = h[PRF_CNT_HITS];
         if (n <= cap) {
             // sorted by (start, end) and reduced to the shortest motif per (start, end) on the device (scan_literal.hip)
-            static_assert(sizeof(prf_hit) == sizeof(prf_hit_dev), "row layouts must agree");
             if (n) {
                 dev_free uniq;
                 HIPCHK(hipMalloc(&uniq.p, n * sizeof(prf_hit_dev)));
@@ -926,6 +963,10 @@ static int literal_device(prf_ctx *c, uint8_t *d_seq, u64 L, bool upper, u32 con
                     HIPCHK(hipMemcpyAsync(rows_out.data() + at, uniq.p, kept * sizeof(prf_hit), hipMemcpyDeviceToHost, c->stream));
                     HIPCHK(hipStreamSynchronize(c->stream));
                 }
+                for (size_t r = at; r < rows_out.size(); r++) {
+                    rows_out[r].start += front;
+                    rows_out[r].end += front;
+                }
                 *launches += 5;
             }
             return PRF_OK;
@@ -938,20 +979,27 @@ static int literal_device(prf_ctx *c, uint8_t *d_seq, u64 L, bool upper, u32 con
 }
 
 static int literal_one(prf_ctx *c, const prf_contig &ct, u32 contig_index, u32 kmin, u32 kmax, u32 min_repeats, u32 min_span,
-                       u64 stop, std::vector<prf_hit> &rows_out, float *ms, u32 *launches, u64 pos_offset) {
+                       u64 stop, std::vector<prf_hit> &rows_out, float *ms, u32 *launches, u64 front) {
     const u64 L = ct.len;
     if (L && !ct.ascii) return fail(PRF_EINVAL, "prf_scan_literal: NULL sequence");
     if (L >= (1ull << 40)) return fail(PRF_EUNSUPPORTED, "prf_scan_literal: input too large (2^40 positions)");
     dev_free seq;
     HIPCHK(hipMalloc(&seq.p, L + 16));
     if (L) HIPCHK(hipMemcpyAsync(seq.p, ct.ascii, L, hipMemcpyHostToDevice, c->stream));
-    return literal_device(c, (uint8_t *)seq.p, L, true, contig_index, kmin, kmax, min_repeats, min_span, stop, rows_out, ms, launches, pos_offset);
+    return literal_device(c, (uint8_t *)seq.p, L, true, contig_index, kmin, kmax, min_repeats, min_span, stop, rows_out, ms, launches, front);
+}
+
+// what the literal lane refuses on a context: a row sink, pipelined scans in flight
+static int literal_preamble(const prf_ctx *c, const char *api) {
+    if (c->sink) return fail(PRF_EUNSUPPORTED, "min_repeats == 1: not with a row sink (the rows of the literal lane are handed over on the host)");
+    if (c->slot[0].seq || c->slot[1].seq) return fail(PRF_EINVAL, "%s: pipelined scans are in flight on this context", api);
+    return PRF_OK;
 }
 
 static int literal_finish(prf_ctx *c, std::vector<prf_hit> &rows, float ms, u32 launches, u64 positions, prf_hits *out,
                           prf_scan_stats *stats) {
-    c->last_nhits = 0;  // the rows of this lane live on the host only
-    c->last_rows = nullptr;
+    c->last.nhits = 0;  // the rows of this lane live on the host only
+    c->last.rows = nullptr;
     if (stats) {
         memset(stats, 0, sizeof *stats);
         stats->scan_ms = stats->phase1_ms = ms;
@@ -978,9 +1026,8 @@ static int literal_genome(prf_ctx *c, const prf_genome *g, u32 kmin, u32 kmax, u
     if (g->sel_on)
         return fail(PRF_EUNSUPPORTED, "min_repeats == 1 scans whole contigs (its rows depend on where a sequence begins and ends): "
                                       "clear the selection of parts (prf_genome_select with n_parts == 0)");
-    if (kmax > 60000) return fail(PRF_EUNSUPPORTED, "max_motif_size %u > 60000", kmax);
-    if (c->sink) return fail(PRF_EUNSUPPORTED, "min_repeats == 1: not with a row sink (the rows of the literal lane are handed over on the host)");
-    if (c->slot[0].seq || c->slot[1].seq) return fail(PRF_EINVAL, "prf_scan_genome: pipelined scans are in flight on this context");
+    const int rc = literal_preamble(c, "prf_scan_genome");
+    if (rc) return rc;
     std::vector<prf_hit> rows;
     float ms = 0;
     u32 launches = 0;
@@ -1003,13 +1050,8 @@ static int literal_genome(prf_ctx *c, const prf_genome *g, u32 kmin, u32 kmax, u
             HIPCHK(prf_launch_lit_unpack(c->stream, g->H, g->L, g->X, g->E, g->base[ci] + lo, n, (uint8_t *)seq.p));
             launches++;
         }
-        const size_t at = rows.size();
-        const int rc = literal_device(c, (uint8_t *)seq.p, n, false, (u32)ci, kmin, kmax, min_repeats, min_span, n, rows, &ms, &launches);
+        const int rc = literal_device(c, (uint8_t *)seq.p, n, false, (u32)ci, kmin, kmax, min_repeats, min_span, n, rows, &ms, &launches, lo);
         if (rc) return rc;
-        for (size_t r = at; r < rows.size(); r++) {
-            rows[r].start += lo;
-            rows[r].end += lo;
-        }
     }
     return literal_finish(c, rows, ms, launches, g->positions, out, stats);
 }
@@ -1019,15 +1061,9 @@ static int literal_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs, co
     if (!c) return fail(PRF_EINVAL, "prf_scan_literal: NULL context");
     if (out) { out->rows = nullptr; out->n = 0; }
     if (n_contigs < 0 || (n_contigs && !contigs)) return fail(PRF_EINVAL, "prf_scan_literal: bad contig array");
-    // same conditions, same wording as the reference's ValueErrors (perfect_repeat_finder.py:23-30)
-    if (kmin < 1) return fail(PRF_EINVAL, "min_motif_size is set to %u. It must be at least 1.", kmin);
-    if (kmax < kmin) return fail(PRF_EINVAL, "max_motif_size is set to %u. It must be at least min_motif_size.", kmax);
-    if (min_repeats < 1) return fail(PRF_EINVAL, "min_repeats is set to %u. It must be at least 1.", min_repeats);
-    if (min_span < 1) return fail(PRF_EINVAL, "min_span is set to %u. It must be at least 1.", min_span);
-    if (kmax > 60000) return fail(PRF_EUNSUPPORTED, "max_motif_size %u > 60000", kmax);
-    if (min_repeats > 1000000u || min_span > (1u << 30)) return fail(PRF_EINVAL, "threshold out of range");
-    if (c->slot[0].seq || c->slot[1].seq) return fail(PRF_EINVAL, "prf_scan_literal: pipelined scans are in flight on this context");
-    if (c->sink) return fail(PRF_EUNSUPPORTED, "min_repeats == 1: not with a row sink (the rows of the literal lane are handed over on the host)");
+    int rc = check_params(kmin, kmax, min_repeats, min_span, 0);
+    if (!rc) rc = literal_preamble(c, "prf_scan_literal");
+    if (rc) return rc;
     HIPCHK(hipSetDevice(c->dev));
     std::vector<prf_hit> rows;
     float ms = 0;
@@ -1046,13 +1082,8 @@ static int literal_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs, co
             w.ascii += lo;
             w.len = hi - lo;
         }
-        const size_t at = rows.size();
-        const int rc = literal_one(c, w, (u32)i, kmin, kmax, min_repeats, min_span, stops ? stops[i] : w.len, rows, &ms, &launches, lo);
+        rc = literal_one(c, w, (u32)i, kmin, kmax, min_repeats, min_span, stops ? stops[i] : w.len, rows, &ms, &launches, lo);
         if (rc) return rc;
-        for (size_t r = at; r < rows.size(); r++) {
-            rows[r].start += lo;
-            rows[r].end += lo;
-        }
         positions += contigs[i].len;
     }
     return literal_finish(c, rows, ms, launches, positions, out, stats);
@@ -1060,28 +1091,15 @@ static int literal_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs, co
 
 int prf_scan_literal(prf_ctx *c, const prf_contig *contig, uint32_t kmin, uint32_t kmax, uint32_t min_repeats, uint32_t min_span,
                      uint64_t stop, prf_hits *out, prf_scan_stats *stats) {
-    try {
-        if (!contig) return fail(PRF_EINVAL, "prf_scan_literal: NULL contig");
-        const u64 stop_ = stop;
-        return literal_impl(c, contig, 1, &stop_, kmin, kmax, min_repeats, min_span, out, stats);
-    } catch (const std::bad_alloc &) {
-        return fail(PRF_ENOMEM, "prf_scan_literal: out of host memory");
-    } catch (...) {
-        return fail(PRF_EHIP, "prf_scan_literal: unexpected exception");
-    }
+    if (!contig) return fail(PRF_EINVAL, "prf_scan_literal: NULL contig");
+    const u64 stop_ = stop;
+    return guarded("prf_scan_literal", [&] { return literal_impl(c, contig, 1, &stop_, kmin, kmax, min_repeats, min_span, out, stats); });
 }
 
 int prf_scan(prf_ctx *c, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax, uint32_t min_repeats,
              uint32_t min_span, uint32_t flags, prf_hits *out, prf_scan_stats *stats) {
-    if (min_repeats == 1) {  // outside the closed form of the packed kernels: the literal lane, contig by contig
-        try {
-            return literal_impl(c, contigs, n_contigs, nullptr, kmin, kmax, min_repeats, min_span, out, stats);
-        } catch (const std::bad_alloc &) {
-            return fail(PRF_ENOMEM, "prf_scan: out of host memory");
-        } catch (...) {
-            return fail(PRF_EHIP, "prf_scan: unexpected exception");
-        }
-    }
+    if (min_repeats == 1)  // outside the closed form of the packed kernels: the literal lane, contig by contig
+        return guarded("prf_scan", [&] { return literal_impl(c, contigs, n_contigs, nullptr, kmin, kmax, min_repeats, min_span, out, stats); });
     prf_genome *g = nullptr;
     int rc = prf_genome_load(c, contigs, n_contigs, kmax, &g);
     if (rc) return rc;
@@ -1099,7 +1117,7 @@ static int scan_async_impl(prf_ctx *c, const prf_genome *g, uint32_t kmin, uint3
     if (!c || !g || !seq_out) return fail(PRF_EINVAL, "prf_scan_genome_async: bad arguments");
     if (g->ctx != c) return fail(PRF_EINVAL, "prf_scan_genome_async: genome belongs to another context");
     if (c->sink) return fail(PRF_EUNSUPPORTED, "prf_scan_genome_async: not with a row sink");
-    if (kmin < 1 || kmax < kmin || min_repeats < 2 || min_span < 1 || kmax > g->kmax_hint)
+    if (min_repeats < 2 || check_params(kmin, kmax, min_repeats, min_span, g->kmax_hint))
         return fail(PRF_EUNSUPPORTED, "prf_scan_genome_async: parameters the synchronous call would refuse or serve otherwise");
     prf_vplan plan;
     if (!prf_vertical_plan(kmin, kmax, min_repeats, min_span, &plan))
@@ -1120,25 +1138,18 @@ static int scan_async_impl(prf_ctx *c, const prf_genome *g, uint32_t kmin, uint3
             HIPCHK(hipHostMalloc((void **)&c->h_async, (PRF_CNT_N + 8) * sizeof(u64), hipHostMallocMapped | hipHostMallocCoherent));
             memset(c->h_async, 0, (PRF_CNT_N + 8) * sizeof(u64));
         }
-        if (c->hit_cap_async < c->hit_cap) {
-            (void)hipFree(c->d_hits_async);
-            c->d_hits_async = nullptr;
-            c->hit_cap_async = 0;
-            HIPCHK(hipMalloc((void **)&c->d_hits_async, c->hit_cap * sizeof(prf_hit_dev)));
-            c->hit_cap_async = c->hit_cap;
-        }
+        const int rc = grow(c->d_hits_async, c->hit_cap_async, c->hit_cap);
+        if (rc) return rc;
         sl.h = c->h_async; sl.rows = c->d_hits_async;
         if (!sl.h_dev) HIPCHK(hipHostGetDevicePointer((void **)&sl.h_dev, c->h_async, 0));
     }
     // (the slabs are shared by the two scans in flight: kernels of one stream run in order, and a scan's gather has read
     // the slabs before the next scan's tiles write them)
+    if (counters_out) *counters_out = c->d_vcounters + (size_t)c->parity * PRF_CNT_N;  // (the block this scan counts in)
+    if (rows_out) *rows_out = sl.rows;
     u64 seq = 0;
-    {
-        if (counters_out) *counters_out = c->d_vcounters + (size_t)c->parity * PRF_CNT_N;  // (the block this scan counts in)
-        if (rows_out) *rows_out = sl.rows;
-        const int rc = launch_fused(c, g, plan, min_repeats, min_span, sl.rows, c->hit_cap, 0u, sl.h_dev, &seq);
-        if (rc) return rc;
-    }
+    const int rc = launch_fused(c, g, plan, min_repeats, min_span, sl.rows, c->hit_cap, 0u, sl.h_dev, &seq);
+    if (rc) return rc;
     sl.seq = seq;
     sl.positions = lv.positions;
     sl.tiles = lv.n;
@@ -1148,33 +1159,43 @@ static int scan_async_impl(prf_ctx *c, const prf_genome *g, uint32_t kmin, uint3
     return PRF_OK;
 }
 
+static prf_ctx::async_slot *slot_of(prf_ctx *c, u64 seq) {
+    return c->slot[0].seq == seq ? &c->slot[0] : (c->slot[1].seq == seq ? &c->slot[1] : nullptr);
+}
+
+// Wait for the scan in a pipelined slot and free the slot, whether the scan succeeded or not.  clear_side_cnt: also zero the
+// pack kernels' row counter (a pack that ran leaves it zero; this is for the pack that failed to launch behind the scan).
+static int retire_slot(prf_ctx *c, prf_ctx::async_slot &sl, bool clear_side_cnt) {
+    const int rc = wait_for_seq(c, sl.seq, sl.h);
+    sl.seq = 0;
+    if (clear_side_cnt) (void)hipMemsetAsync(c->d_side_cnt, 0, sizeof(u64), c->stream);
+    return rc;
+}
+
 int prf_scan_genome_async(prf_ctx *c, const prf_genome *g, uint32_t kmin, uint32_t kmax, uint32_t min_repeats, uint32_t min_span,
                           uint64_t *seq_out) {
-    try {
-        return scan_async_impl(c, g, kmin, kmax, min_repeats, min_span, seq_out);
-    } catch (...) {
-        return fail(PRF_EHIP, "prf_scan_genome_async: unexpected exception");
-    }
+    return guarded("prf_scan_genome_async", [&] { return scan_async_impl(c, g, kmin, kmax, min_repeats, min_span, seq_out); });
 }
 
 // A pipelined scan whose rows leave as 8-byte wire words without the host in between: the pack kernels are enqueued behind the
 // scan's gather on the library's stream and read the row count from the scan's counter block (which the NEXT scan's gather
-// clears: stream order keeps it alive until then).
+// clears: stream order keeps it alive until then).  If the pack cannot be launched, the scan is collected here: the call
+// fails and leaves the context as it was before it.
 int prf_scan_genome_async_packed(prf_ctx *c, const prf_genome *g, uint32_t kmin, uint32_t kmax, uint32_t min_repeats, uint32_t min_span,
                                  void *dst_device, uint64_t capacity_rows, uint64_t side_capacity, uint64_t *seq_out) {
-    try {
+    return guarded("prf_scan_genome_async_packed", [&]() -> int {
         if (!dst_device) return fail(PRF_EINVAL, "prf_scan_genome_async_packed: no destination");
         if (kmax > 511u) return fail(PRF_EUNSUPPORTED, "the 8-byte wire rows hold motif sizes up to 511 (max_motif_size %u)", kmax);
         const u64 *counters = nullptr;
         const prf_hit_dev *rows = nullptr;
         const int rc = scan_async_impl(c, g, kmin, kmax, min_repeats, min_span, seq_out, &counters, &rows);
         if (rc) return rc;
-        HIPCHK(prf_launch_pack_rows_dev(c->stream, rows, counters + PRF_CNT_ROWS, capacity_rows, g->d_base, (u64 *)dst_device, side_capacity,
-                                        c->d_side_cnt));
-        return PRF_OK;
-    } catch (...) {
-        return fail(PRF_EHIP, "prf_scan_genome_async_packed: unexpected exception");
-    }
+        const hipError_t e = prf_launch_pack_rows_dev(c->stream, rows, counters + PRF_CNT_ROWS, capacity_rows, g->d_base,
+                                                      (u64 *)dst_device, side_capacity, c->d_side_cnt);
+        if (e == hipSuccess) return PRF_OK;
+        (void)retire_slot(c, *slot_of(c, *seq_out), true);
+        return fail(e == hipErrorOutOfMemory ? PRF_ENOMEM : PRF_EHIP, "prf_launch_pack_rows_dev failed: %s", hipGetErrorString(e));
+    });
 }
 
 // Everything enqueued on the library's stream so far happens before whatever is enqueued on `other_stream` (a hipStream_t)
@@ -1189,32 +1210,15 @@ int prf_stream_wait_for(prf_ctx *c, void *other_stream) {
 
 int prf_scan_wait(prf_ctx *c, uint64_t seq, prf_scan_stats *stats) {
     if (!c || !seq) return fail(PRF_EINVAL, "prf_scan_wait: bad arguments");
-    prf_ctx::async_slot *sl = c->slot[0].seq == seq ? &c->slot[0] : (c->slot[1].seq == seq ? &c->slot[1] : nullptr);
+    prf_ctx::async_slot *sl = slot_of(c, seq);
     if (!sl) return fail(PRF_EINVAL, "prf_scan_wait: scan %llu is not in flight", (unsigned long long)seq);
-    int rc = wait_for_seq(c, seq, sl->h);
-    sl->seq = 0;
+    const int rc = retire_slot(c, *sl, false);
     if (rc) return rc;
-    const u64 nhits = sl->h[PRF_CNT_ROWS];
-    u64 ncand = 0;
-    for (int sh = 0; sh < PRF_CNT_NSHARD; sh++) ncand += sl->h[PRF_CNT_SHARD0 + sh * PRF_CNT_SHARD_STRIDE + PRF_SH_CAND];
-    if (sl->h[PRF_CNT_HIT_OVF] > c->slab_cap || nhits > c->hit_cap || sl->h[PRF_CNT_LONG_OVF])
+    const pass_result r = read_fused(sl->h);
+    if (sl->h[PRF_CNT_HIT_OVF] > c->slab_cap || r.nhits > c->hit_cap || sl->h[PRF_CNT_LONG_OVF])
         return fail(PRF_EUNSUPPORTED, "prf_scan_wait: the buffers sized by the last synchronous scan overflowed; scan synchronously");
-    c->last_nhits = nhits;
-    c->last_kmax = sl->kmax;
-    c->last_rows = sl->rows;
-    c->last_sorted = sl->h[PRF_CNT_UNSORTED] == 0;
-    if (stats) {
-        memset(stats, 0, sizeof *stats);
-        stats->sorted_on_device = c->last_sorted ? 1u : 0u;
-        stats->tiles_launched = sl->tiles;
-        stats->positions = sl->positions;
-        stats->packed_bytes = (sl->positions + 3) / 4;
-        stats->n_candidates = ncand;
-        stats->n_hits = nhits;
-        stats->n_launches = 2;
-        stats->path = 1;
-        stats->seq = seq;
-    }
+    c->last = {sl->rows, r.nhits, sl->kmax};
+    if (stats) fill_stats(stats, r, 1, sl->positions, sl->tiles, seq);
     return PRF_OK;
 }
 
@@ -1228,16 +1232,12 @@ int prf_set_row_sink(prf_ctx *c, void *dst_device, uint64_t capacity_rows) {
 int prf_last_hits_to_device(prf_ctx *c, void *dst, uint64_t capacity_rows, int count_row, uint64_t *n_rows) {
     if (!c || !n_rows || ((capacity_rows || count_row) && !dst)) return fail(PRF_EINVAL, "prf_last_hits_to_device: bad arguments");
     HIPCHK(hipSetDevice(c->dev));
-    *n_rows = c->last_nhits;
-    const u64 n = std::min<u64>(c->last_nhits, capacity_rows);
-    if (n && dst != (void *)c->last_rows)
-        HIPCHK(hipMemcpyAsync(dst, c->last_rows, n * sizeof(prf_hit_dev), hipMemcpyDeviceToDevice, c->stream));
-    if (count_row) {  // staged in the spare words behind the counter block (pinned); the stream is drained below
-        u64 *stage = c->h_counters + PRF_CNT_N + 2;
-        stage[0] = n; stage[1] = 0; stage[2] = 0;
-        HIPCHK(hipMemcpyAsync((prf_hit_dev *)dst + capacity_rows, stage, sizeof(prf_hit_dev), hipMemcpyHostToDevice, c->stream));
-    }
-    if (n || count_row) HIPCHK(hipStreamSynchronize(c->stream));
+    *n_rows = c->last.nhits;
+    const u64 n = std::min<u64>(c->last.nhits, capacity_rows);
+    if (n && dst != (void *)c->last.rows)
+        HIPCHK(hipMemcpyAsync(dst, c->last.rows, n * sizeof(prf_hit_dev), hipMemcpyDeviceToDevice, c->stream));
+    if (count_row) return write_count_record(c, (prf_hit_dev *)dst, capacity_rows, n);
+    if (n) HIPCHK(hipStreamSynchronize(c->stream));
     return PRF_OK;
 }
 
@@ -1303,33 +1303,27 @@ static int genome_select_impl(prf_genome *g, const prf_part *parts, int n_parts)
 }
 
 int prf_genome_select(prf_genome *g, const prf_part *parts, int n_parts) {
-    try {
-        return genome_select_impl(g, parts, n_parts);
-    } catch (const std::bad_alloc &) {
-        return fail(PRF_ENOMEM, "prf_genome_select: out of host memory");
-    } catch (...) {
-        return fail(PRF_EHIP, "prf_genome_select: unexpected exception");
-    }
+    return guarded("prf_genome_select", [&] { return genome_select_impl(g, parts, n_parts); });
 }
 
 int prf_last_hits_packed_to_device(prf_ctx *c, const prf_genome *g, void *dst, uint64_t capacity_rows, uint64_t side_capacity,
                                    uint64_t *n_rows) {
     if (!c || !g || g->ctx != c || !n_rows || !dst) return fail(PRF_EINVAL, "prf_last_hits_packed_to_device: bad arguments");
     HIPCHK(hipSetDevice(c->dev));
-    *n_rows = c->last_nhits;
-    if (c->last_kmax > 511u)  // (such rows used to leave with a truncated motif size)
+    *n_rows = c->last.nhits;
+    if (c->last.kmax > 511u)  // (such rows used to leave with a truncated motif size)
         return fail(PRF_EUNSUPPORTED, "the 8-byte wire rows hold motif sizes up to 511; the last scan went up to %u -- hand its rows over whole "
-                    "(prf_last_hits_to_device)", c->last_kmax);
-    if (c->last_nhits > capacity_rows)
+                    "(prf_last_hits_to_device)", c->last.kmax);
+    if (c->last.nhits > capacity_rows)
         return fail(PRF_EINVAL, "the packed row buffer holds %llu rows, the scan found %llu", (unsigned long long)capacity_rows,
-                    (unsigned long long)c->last_nhits);
+                    (unsigned long long)c->last.nhits);
     u64 *words = (u64 *)dst;
     // (a spare device word: the generic path's counters are idle here; spare pinned words behind the counter block,
     // written by the device)
     u64 *side_cnt = c->d_counters + PRF_CNT_CAND;
     HIPCHK(hipMemsetAsync(side_cnt, 0, sizeof(u64), c->stream));
     volatile u64 *stage = c->h_counters + PRF_CNT_N + 2;
-    HIPCHK(prf_launch_pack_rows(c->stream, c->last_rows, c->last_nhits, g->d_base, words, capacity_rows, side_capacity, side_cnt,
+    HIPCHK(prf_launch_pack_rows(c->stream, c->last.rows, c->last.nhits, g->d_base, words, capacity_rows, side_capacity, side_cnt,
                                 c->h_counters_dev + PRF_CNT_N + 2));
     HIPCHK(hipStreamSynchronize(c->stream));
     const u64 n_side = stage[0];
@@ -1348,7 +1342,7 @@ int prf_genome_contig_bases(const prf_genome *g, uint64_t *bases, uint64_t capac
 
 int prf_genome_footprint(const prf_genome *g, uint64_t *device_bytes, uint64_t *positions) {
     if (!g || !device_bytes || !positions) return fail(PRF_EINVAL, "prf_genome_footprint: bad arguments");
-    const u64 tot = PRF_FRONT_PAD + g->nwords + g->padw;      // words of one linear plane (genome_load_impl)
+    const u64 tot = PRF_FRONT_PAD + g->nwords + g->padw;      // words of one linear plane (alloc_plane)
     const u64 ntiles = g->G / PRF_TILE;
     u64 bytes = 3 * tot * 8;                                   // H, L, X
     if (g->d_E) bytes += 5 * tot * 8 + 5 * sizeof(u64 *);      // the code planes of the letters outside ACGTN

@@ -140,8 +140,12 @@ bool prf_vertical_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vp
         // (long, plenty of independent arithmetic) and the flag waves (they wait at the barrier anyway) at 0.  Measured on
         // the default workload (tools/prio_sweep.sh, gpurun_out/prio_sweep*.txt): 0.775 ms without priorities, 0.748-0.757
         // with any setting that raises records and rows; random sequence (few candidates) is indifferent.
-        // PRF_PRIO (diagnostic) overrides.
+        // PRF_PRIO overrides in a diagnostic build (PRF_DIAG).
+#ifdef PRF_DIAG
         static const u32 prio_cfg = getenv("PRF_PRIO") ? (u32)strtoul(getenv("PRF_PRIO"), nullptr, 0) : 0xA02u;
+#else
+        const u32 prio_cfg = 0xA02u;
+#endif
         plan->prio = prio_cfg;
         const u32 busiest = *std::max_element(load.begin(), load.end());
         plan->slack_waves = 0;

@@ -552,8 +552,13 @@ hipError_t prf_launch_lit_upper(hipStream_t st, uint8_t *s, u64 n, u64 *bad_pos)
 
 hipError_t prf_launch_lit_events(hipStream_t st, const uint8_t *s, u64 L, u32 kmin, u32 kmax, u32 min_repeats, u32 min_span,
                                  u64 stop, u32 contig, prf_hit_dev *rows, u64 cap, u64 *counters) {
-    // motif sizes up to 63: 64 positions per thread in registers (PRF_LIT_BYTEWISE=1: the byte routine for every size, diagnostic)
+    // motif sizes up to 63: 64 positions per thread in registers (a diagnostic build with PRF_LIT_BYTEWISE=1: the byte routine for
+    // every size)
+#ifdef PRF_DIAG
     static const bool bytewise = getenv("PRF_LIT_BYTEWISE") && atoi(getenv("PRF_LIT_BYTEWISE")) != 0;
+#else
+    const bool bytewise = false;
+#endif
     if (!bytewise && kmin <= 63u) {
         const u32 k_hi = kmax < 63u ? kmax : 63u;
         const u64 Lk = L > kmin ? L - kmin : 0;

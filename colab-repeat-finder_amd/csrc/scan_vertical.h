@@ -47,7 +47,9 @@ struct prf_vscan_args {
     const uint4 *tile_info;        // [tile]: {contig, 0, contig base lo, hi}
     u64 *counters;                 // this scan's counter block (zero when the kernel starts)
     u64 *dbg;                      // diagnostic (PRF_STAMPS) builds only; nullptr otherwise
-    u32 skip;                      // diagnostic (PRF_SKIP): phases left out to time the others; 0 in every real scan
+#ifdef PRF_DIAG
+    u32 skip;                      // PRF_SKIP: phases left out to time the others (diagnostic builds only; read through vscan_skip)
+#endif
     prf_vplan plan;
 };
 

@@ -1205,6 +1205,16 @@ struct NextRegs {
     }
 };
 
+// The phases a diagnostic build leaves out (PRF_SKIP); the constant 0 in the product, where the branches compile away
+__device__ __forceinline__ u32 vscan_skip(const prf_vscan_args &g) {
+#ifdef PRF_DIAG
+    return g.skip;
+#else
+    (void)g;
+    return 0u;
+#endif
+}
+
 template <int NC>
 __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
     constexpr u32 R1_OFF = (u32)SMEM_HDR, R1_BYTES = (u32)(2 * RG * NC * 16);
@@ -1338,7 +1348,7 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
 #endif
     {
         u32 allow = hasx ? ~nostart[lane] : ~0u;
-        if (g.skip & 1u) allow = 0u;  // (diagnostic, PRF_SKIP: no flags, no records)
+        if (vscan_skip(g) & 1u) allow = 0u;  // (diagnostic, PRF_SKIP: no flags, no records)
         run_tasks<NC>((prf_lds_cu4 *)vimg, hotw, g.plan, wave, lane, hasx, allow, em, task_dbg);
     }
     // ---- 3a. R1 <- the window of the linear planes H and L (tile - 128 .. tile + 65536 + 1536 positions), in 16-byte units: unit
@@ -1431,9 +1441,9 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
 #ifdef PRF_STAMPS
         if (g.dbg && tid == 0) g.dbg[((u64)slot * MAX_WAVES + 0) * 16 + 11] = (u64)n_flags | ((u64)n_recs << 32);  // (wave 0 has three tasks)
 #endif
-        if (g.skip & 2u) n_flags = 0;   // (diagnostic) the flags are listed but not verified
-        if (g.skip & 4u) n_recs = 0;    // (diagnostic) the same for the records
-        verify_all((prf_lds_cu64 *)recs, n_recs, (prf_lds_cu32 *)bitems, (g.skip & 8u) ? 0u : g.plan.n_group_k, (prf_lds_cu16 *)hotw, n_flags, xw, (u32)tid, task_dbg);
+        if (vscan_skip(g) & 2u) n_flags = 0;   // (diagnostic) the flags are listed but not verified
+        if (vscan_skip(g) & 4u) n_recs = 0;    // (diagnostic) the same for the records
+        verify_all((prf_lds_cu64 *)recs, n_recs, (prf_lds_cu32 *)bitems, (vscan_skip(g) & 8u) ? 0u : g.plan.n_group_k, (prf_lds_cu16 *)hotw, n_flags, xw, (u32)tid, task_dbg);
     }
     set_prio((g.plan.prio >> 10) & 3u);
     if (ticket_thread) {  // the next slot and its entry, for everybody behind the barrier
@@ -1468,7 +1478,7 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
     const u64 nw = *(prf_lds_u64 *)next_words;  // (one read)
     slot_next = (u32)__builtin_amdgcn_readfirstlane((int)(u32)nw);
     const u32 entry_next = (u32)(nw >> 32);
-    const u32 n_rows = (g.skip & 16u) ? 0u : (u32)__builtin_amdgcn_readfirstlane((int)cnt[CNT_ROWS]);  // (diagnostic: rows counted as none)
+    const u32 n_rows = (vscan_skip(g) & 16u) ? 0u : (u32)__builtin_amdgcn_readfirstlane((int)cnt[CNT_ROWS]);  // (diagnostic: rows counted as none)
     const u32 n_long = (u32)__builtin_amdgcn_readfirstlane((int)cnt[CNT_LONG]);
     u64 *slab = g.slabs + (u64)slot * g.slab_cap;
     const u32 n_store = n_rows < g.slab_cap ? n_rows : g.slab_cap;
@@ -1480,7 +1490,7 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
     // is gone: the gather adds the first level up itself).
     if (tid == 0) {
         g.slab_count[slot] = n_rows;
-        if (n_store && !(g.skip & 32u)) atomicAdd(&g.block_sum[slot >> g.gather_shift], n_store);
+        if (n_store && !(vscan_skip(g) & 32u)) atomicAdd(&g.block_sum[slot >> g.gather_shift], n_store);
     }
 
     // ---- 4. the tile's rows, sorted by (start, end), into its slab.  Rank of a row = number of rows with a smaller key; keys
@@ -1565,7 +1575,7 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
             if (P >= 2u) rank += (u32)__builtin_amdgcn_update_dpp(0, (int)rank, 0xB1, 0xF, 0xF, true);
             if (P >= 4u) rank += (u32)__builtin_amdgcn_update_dpp(0, (int)rank, 0x4E, 0xF, 0xF, true);
             if (P >= 8u) rank += (u32)__builtin_amdgcn_update_dpp(0, (int)rank, 0x141, 0xF, 0xF, true);
-            if (row < n_rows && part == 0 && rank < g.slab_cap && !(g.skip & 64u)) slab[rank] = (u64)mine | ((u64)kv << 32);
+            if (row < n_rows && part == 0 && rank < g.slab_cap && !(vscan_skip(g) & 64u)) slab[rank] = (u64)mine | ((u64)kv << 32);
         }
     }
     if ((u32)tid < n_long && (u32)tid < PRF_LONG_PER_TILE)
@@ -1848,9 +1858,12 @@ static u32 resident_per_cu(u32 nc, u32 lds) {
 
 hipError_t prf_vertical_launch(hipStream_t s, const prf_vscan_args &args) {
     if (args.n_launch == 0) return hipSuccess;
-    // PRF_LDS_PAD (diagnostic): extra dynamic LDS per workgroup, to measure the scan at a lower occupancy
+    u32 lds = args.plan.lds_bytes;
+#ifdef PRF_DIAG
+    // PRF_LDS_PAD: extra dynamic LDS per workgroup, to measure the scan at a lower occupancy
     static const u32 lds_pad = getenv("PRF_LDS_PAD") ? (u32)atoi(getenv("PRF_LDS_PAD")) : 0u;
-    const u32 lds = args.plan.lds_bytes + lds_pad;
+    lds += lds_pad;
+#endif
     static int n_cu = 0;
     if (n_cu == 0) {
         int dev = 0;
@@ -1863,7 +1876,9 @@ hipError_t prf_vertical_launch(hipStream_t s, const prf_vscan_args &args) {
         cache_per_cu = resident_per_cu(args.plan.nc, lds);
         cache_lds = lds;
         cache_nc = args.plan.nc;
+#ifdef PRF_DIAG
         if (getenv("PRF_DEBUG")) fprintf(stderr, "[prf] fused kernel: nc %u, %u bytes of LDS, %u workgroups per CU\n", args.plan.nc, lds, cache_per_cu);
+#endif
     }
     const dim3 grid(std::min(args.n_launch, cache_per_cu * (u32)n_cu)), block(NTH);
     switch (args.plan.nc) {

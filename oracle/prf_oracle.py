@@ -25,7 +25,15 @@ def build(force=False):
     if os.environ.get("PRF_ORACLE_LIB"):
         return _LIB_PATH                      # built by whoever set the variable (tests/test_asan_host.py)
     if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < os.path.getmtime(src):
-        subprocess.check_call(["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-Wall", "-o", _LIB_PATH, src])
+        # compiled to a file of this process, then renamed into place: processes that build at the same time (the ranks
+        # of a multi-process test) never load a half-written library
+        tmp = os.path.join(_HERE, f"libprf_oracle.{os.getpid()}.tmp.so")
+        try:
+            subprocess.check_call(["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-Wall", "-o", tmp, src])
+            os.replace(tmp, _LIB_PATH)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
     return _LIB_PATH
 
 

@@ -51,3 +51,16 @@ def test_no_cpu_fallback_without_a_device():
     prf_native._default_ctx.clear()
     with pytest.raises(prf_native.PrfError):
         prf.detect_repeats("ACACACACACAC", argparse.Namespace(min_motif_size=1, max_motif_size=6, min_repeats=3, min_span=9))
+
+
+def test_product_library_holds_no_diagnostic_switch():
+    """The switches that exist for diagnosis are read by a diagnostic build only (make EXTRA=-DPRF_DIAG ...): libprf.so does
+    not hold their names.  PRF_SCAN_TIMEOUT_S, an operational limit, stays -- which also shows that the check reads the library."""
+    path = os.path.join(PKG, "libprf.so")
+    if not os.path.exists(path):
+        import __graft_entry__
+        __graft_entry__.build()
+    data = open(path, "rb").read()
+    for name in ("PRF_SKIP", "PRF_GATHER_SHIFT", "PRF_LDS_PAD", "PRF_PRIO", "PRF_LIT_BYTEWISE", "PRF_DEBUG"):
+        assert name.encode() not in data, f"libprf.so reads the diagnostic switch {name}"
+    assert b"PRF_SCAN_TIMEOUT_S" in data

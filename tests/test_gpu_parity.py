@@ -1030,3 +1030,43 @@ def test_randomised_differential_stress():
                          capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     assert "0 mismatches" in res.stdout
+
+
+_DIAG_SWITCHES_CHILD = r"""
+import sys
+sys.path[:0] = sys.argv[1:3]
+import prf_native
+import synth
+from oracle import prf_oracle
+seq = bytearray(synth.chr_standin(length=300_000, seed=7, n_head=20_000, n_tail=1_000).tobytes())
+seq[150_000:150_090] = b"CAG" * 30
+seq = bytes(seq)
+ctx = prf_native.Context(0)
+g = ctx.load([seq], 50)
+# the parameter sets of smoke() (fused, fused, literal lane) and the generic kernels
+for (kmin, kmax, r, span), flags, path in [((1, 50, 3, 9), 0, 1), ((2, 6, 3, 9), 0, 1), ((1, 8, 1, 7), 0, 2),
+                                           ((1, 50, 3, 9), prf_native.SCAN_FORCE_GENERIC, 0)]:
+    rows, st = g.scan(kmin, kmax, r, span, flags=flags)
+    got = [(int(x["start"]), int(x["end"]), int(x["k"])) for x in rows]
+    want = [(s, e, ml if r == 1 else k) for s, e, ml, k in prf_oracle.detect_rows(seq, kmin, kmax, r, span)]
+    assert st.path == path and got == want and len(got) > 100, (kmin, kmax, r, span, flags, st.path, len(got), len(want))
+g.free()
+ctx.close()
+print("rows equal the oracle's on every lane")
+"""
+
+
+def test_diagnostic_switches_do_not_change_the_product_library():
+    """PRF_SKIP, PRF_GATHER_SHIFT, PRF_LDS_PAD, PRF_PRIO, PRF_LIT_BYTEWISE and PRF_DEBUG are read by a diagnostic build only
+    (make EXTRA=-DPRF_DIAG ...): set in the environment of a fresh process, they change no row of the fused, literal and
+    generic lanes, and the library prints nothing."""
+    import subprocess
+    import sys
+    from conftest import PKG, ROOT
+    env = dict(os.environ, PRF_SKIP="31", PRF_GATHER_SHIFT="6", PRF_LDS_PAD="8192", PRF_PRIO="0", PRF_LIT_BYTEWISE="1",
+               PRF_DEBUG="1")
+    res = subprocess.run([sys.executable, "-c", _DIAG_SWITCHES_CHILD, ROOT, PKG], cwd=ROOT, env=env, capture_output=True, text=True,
+                         timeout=300)
+    assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-1500:]
+    assert "rows equal the oracle's on every lane" in res.stdout
+    assert "[prf]" not in res.stderr, res.stderr[-1500:]

@@ -1,5 +1,7 @@
 """Diagnostic: the same scan again and again must give the same rows (synchronous and pipelined calls).
-usage (GPU box): [NC=contigs] [N=scans] [PRF_SKIP=..] python tools/nondet_check.py"""
+usage (GPU box): [NC=contigs] [N=scans] python tools/nondet_check.py
+PRF_SKIP=.. is read by the diagnostic build only: make -C colab-repeat-finder_amd/csrc EXTRA=-DPRF_DIAG BUILD=build_ab
+OUT=../libprf_diag.so, then PRF_LIB=colab-repeat-finder_amd/libprf_diag.so PRF_SKIP=.. python tools/nondet_check.py"""
 import os, sys
 import numpy as np
 sys.path.insert(0, "colab-repeat-finder_amd"); sys.path.insert(0, ".")

@@ -1,5 +1,7 @@
 #!/bin/bash
 # issue-priority sweep on the default workload (diagnostic): PRF_PRIO = stage | busy<<2 | slack<<4 | flags<<6 | records<<8 | rows<<10
+# PRF_PRIO is read by the diagnostic build only (make -C colab-repeat-finder_amd/csrc EXTRA=-DPRF_DIAG BUILD=build_ab OUT=../libprf_diag.so)
+export PRF_LIB=colab-repeat-finder_amd/libprf_diag.so
 mkdir -p gpurun_out/prio
 for cfg in 0xA02 0x000 0xA00 0xE02 0xF02 0xA42 0xAC2 0xA82 0xA03 0xA06 0xA0A 0xA0E 0xE42 0x602 0x202 0xA02; do
   PRF_PRIO=$cfg python bench.py --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/prio/$cfg.json 2>/dev/null
