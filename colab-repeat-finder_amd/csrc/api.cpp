@@ -1108,6 +1108,247 @@ int prf_scan(prf_ctx *c, const prf_contig *contigs, int n_contigs, uint32_t kmin
     return rc;
 }
 
+// ---- interrupted repeats (scan_interrupted.hip) ----
+// Whole sequences, one call: upload + upper-case (+ the first byte that is not a letter) + N-trimming on the device, the walk
+// (one lane per (sequence, k); candidate lists grow by running again with the exact counts), then emission + sort.
+namespace {
+struct dev_buf {
+    void *p = nullptr;
+    ~dev_buf() { if (p) (void)hipFree(p); }
+    int alloc(size_t bytes) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        HIPCHK(hipMalloc(&p, bytes ? bytes : 16));
+        return PRF_OK;
+    }
+};
+}  // namespace
+
+static int interrupted_check(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, u32 max_interruptions, u32 memo_stride) {
+    int rc = check_params(kmin, kmax, min_repeats, min_span, 0);
+    if (rc) return rc;
+    if (max_interruptions < 1)
+        return fail(PRF_EINVAL, "max_interruptions is %u: prf_scan_interrupted serves max_interruptions >= 1 (0 is prf_scan's perfect path)",
+                    max_interruptions);
+    if (min_repeats < 2)
+        return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: min_repeats == 1 is not supported with interruptions (min_repeats >= 2)");
+    if (kmax > 64) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: max_motif_size %u > 64 (the phase set is one 64-bit mask)", kmax);
+    if (memo_stride & (memo_stride - 1u)) return fail(PRF_EINVAL, "prf_scan_interrupted: memo_stride %u is not a power of two", memo_stride);
+    return PRF_OK;
+}
+
+static int interrupted_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs, u32 kmin, u32 kmax, u32 min_repeats, u32 min_span,
+                            u32 max_int, u32 memo_stride, u64 memo_slots, prf_ihits *out, prf_scan_stats *stats, uint64_t *counters_out) {
+    if (out) { out->rows = nullptr; out->n = 0; }
+    int rc = interrupted_check(kmin, kmax, min_repeats, min_span, max_int, memo_stride);
+    if (rc) return rc;
+    if (!c) return fail(PRF_EINVAL, "prf_scan_interrupted: NULL context");
+    if (n_contigs < 0 || (n_contigs && !contigs)) return fail(PRF_EINVAL, "prf_scan_interrupted: bad contig array");
+    for (int i = 0; i < n_contigs; i++) {
+        if (contigs[i].len && !contigs[i].ascii) return fail(PRF_EINVAL, "prf_scan_interrupted: NULL sequence");
+        if (contigs[i].len >= (1ull << 40)) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: input too large (2^40 positions)");
+    }
+    if (c->slot[0].seq || c->slot[1].seq) return fail(PRF_EINVAL, "prf_scan_interrupted: pipelined scans are in flight on this context");
+    HIPCHK(hipSetDevice(c->dev));
+    const u32 nk = kmax - kmin + 1, n_seq = (u32)n_contigs;
+    const u64 n_lanes64 = (u64)n_seq * nk;
+    if (n_lanes64 > 0x7fffffffull) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: too many (sequence, motif size) lanes");
+    const u32 n_lanes = (u32)n_lanes64;
+
+    // host plan: sequence placement (16-byte aligned, 16 readable bytes behind each), trim chunks, lanes
+    std::vector<u64> seq_base(std::max<u32>(1, n_seq)), chunks;
+    u64 total = 0, positions = 0;
+    for (u32 i = 0; i < n_seq; i++) {
+        seq_base[i] = total;
+        total += (contigs[i].len + 16 + 15) & ~15ull;
+        positions += contigs[i].len;
+        for (u64 b = 0; b < contigs[i].len; b += 4096) {
+            chunks.push_back(i);
+            chunks.push_back(b);
+            chunks.push_back(std::min<u64>(contigs[i].len, b + 4096));
+        }
+    }
+    const u32 n_chunks = (u32)(chunks.size() / 3);
+    std::vector<prf_ilane> lanes(std::max<u32>(1, n_lanes));
+    std::vector<u64> cand_cap(n_lanes);
+    // about one candidate per five positions on random sequence (every episode that jumps back ends in one): room for one per
+    // four, so that the walk usually runs once
+    for (u32 li = 0; li < n_lanes; li++) cand_cap[li] = contigs[li / nk].len / 4 + 16;
+    u64 memo_total = 0, ep_total = 0;
+    for (u32 li = 0; li < n_lanes; li++) {
+        prf_ilane &ln = lanes[li];
+        const u64 len = contigs[li / nk].len;
+        ln.seq = li / nk;
+        ln.k = kmin + li % nk;
+        ln.seq_base = seq_base[ln.seq];
+        ln.memo_slots = memo_stride ? std::min<u64>(memo_slots, len / memo_stride + 1) : 0;
+        ln.memo_off = memo_total;
+        memo_total += ln.memo_slots;
+        ln.ep_cap = ln.memo_slots ? len / 4 + 64 : 0;  // episodes land at strictly increasing positions: at most len of them
+        ln.ep_off = ep_total;
+        ep_total += ln.ep_cap;
+    }
+
+    dev_buf d_seq, d_base, d_chunks, d_fl, d_lanes, d_cands, d_cnt, d_memo, d_eps, d_ctr;
+    if ((rc = d_seq.alloc(total + 16)) || (rc = d_base.alloc(seq_base.size() * 8)) || (rc = d_chunks.alloc(chunks.size() * 8)) ||
+        (rc = d_fl.alloc(2 * 8 * (size_t)std::max<u32>(1, n_seq))) || (rc = d_lanes.alloc(lanes.size() * sizeof(prf_ilane))) ||
+        (rc = d_cnt.alloc(8 * (size_t)std::max<u32>(1, n_lanes))) || (rc = d_memo.alloc(memo_total * sizeof(prf_imemo))) ||
+        (rc = d_eps.alloc(ep_total * 4)) || (rc = d_ctr.alloc(8 * 8)))
+        return rc;
+    hipStream_t st = c->stream;
+    HIPCHK(hipMemsetAsync(d_seq.p, 'N', total + 16, st));  // the gaps are letters: the symbol check passes over them
+    for (u32 i = 0; i < n_seq; i++)
+        if (contigs[i].len) HIPCHK(hipMemcpyAsync((uint8_t *)d_seq.p + seq_base[i], contigs[i].ascii, contigs[i].len, hipMemcpyHostToDevice, st));
+    std::vector<u64> fl(2 * (size_t)std::max<u32>(1, n_seq));
+    for (size_t i = 0; i < fl.size(); i += 2) { fl[i] = ~0ull; fl[i + 1] = 0; }
+    HIPCHK(hipMemcpyAsync(d_base.p, seq_base.data(), seq_base.size() * 8, hipMemcpyHostToDevice, st));
+    if (!chunks.empty()) HIPCHK(hipMemcpyAsync(d_chunks.p, chunks.data(), chunks.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_fl.p, fl.data(), fl.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_ctr.p, 0, 8 * 8, st));
+    HIPCHK(hipMemsetAsync(d_ctr.p, 0xFF, 8, st));  // word 0: first byte that is not a letter
+    u32 launches = 0;
+    HIPCHK(hipEventRecord(c->ev[0], st));
+    if (total) HIPCHK(prf_launch_lit_upper(st, (uint8_t *)d_seq.p, total, (u64 *)d_ctr.p));
+    HIPCHK(prf_launch_int_trim(st, (const uint8_t *)d_seq.p, (const u64 *)d_base.p, (const u64 *)d_chunks.p, n_chunks, (u64 *)d_fl.p));
+    launches += 2;
+    u64 h_ctr[8];
+    HIPCHK(hipMemcpyAsync(h_ctr, d_ctr.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h_ctr[0] != ~0ull) {
+        const u64 at = h_ctr[0];
+        u32 ci = (u32)(std::upper_bound(seq_base.begin(), seq_base.begin() + n_seq, at) - seq_base.begin()) - 1;
+        return fail(PRF_ESYMBOL, "unsupported symbol at contig %u position %llu: only letters are accepted (A, C, G, T, N and -- as "
+                    "ordinary symbols, like the reference -- any other letter, in either case)", ci, (unsigned long long)(at - seq_base[ci]));
+    }
+
+    std::vector<u64> cnt(std::max<u32>(1, n_lanes));
+    for (int attempt = 0;; attempt++) {
+        u64 cand_total = 0;
+        for (u32 li = 0; li < n_lanes; li++) {
+            lanes[li].cand_off = cand_total;
+            lanes[li].cand_cap = cand_cap[li];
+            cand_total += cand_cap[li];
+        }
+        if ((rc = d_cands.alloc(cand_total * sizeof(prf_icand)))) return rc;
+        HIPCHK(hipMemcpyAsync(d_lanes.p, lanes.data(), lanes.size() * sizeof(prf_ilane), hipMemcpyHostToDevice, st));
+        if (memo_total) HIPCHK(hipMemsetAsync(d_memo.p, 0xFF, memo_total * sizeof(prf_imemo), st));  // no state has pos ~0
+        HIPCHK(hipMemsetAsync((u64 *)d_ctr.p + 1, 0, 7 * 8, st));
+        HIPCHK(hipEventRecord(c->ev[1], st));
+        HIPCHK(prf_launch_int_walk(st, (const uint8_t *)d_seq.p, (const prf_ilane *)d_lanes.p, n_lanes, (const u64 *)d_fl.p, min_repeats,
+                                   min_span, max_int, memo_stride, (prf_icand *)d_cands.p, (u64 *)d_cnt.p, (prf_imemo *)d_memo.p,
+                                   (u32 *)d_eps.p, (u64 *)d_ctr.p + 1));
+        HIPCHK(hipEventRecord(c->ev[2], st));
+        launches++;
+        HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, 8 * (size_t)n_lanes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_ctr, d_ctr.p, 8 * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        bool over = false;
+        for (u32 li = 0; li < n_lanes; li++) {
+            if (cnt[li] > (u64)0x3fffffff) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: more than 2^30 candidates on one lane");
+            if (cnt[li] > cand_cap[li]) { over = true; cand_cap[li] = cnt[li]; }
+        }
+        if (!over) break;
+        if (attempt >= 1) return fail(PRF_EHIP, "prf_scan_interrupted: the candidate counts changed between two runs");
+    }
+    float walk_ms = 0;
+    HIPCHK(hipEventElapsedTime(&walk_ms, c->ev[1], c->ev[2]));
+
+    // emission: one lane per sequence, a hash of the emitted (start, end) per sequence
+    std::vector<u64> hoff(std::max<u32>(1, n_seq)), hsize(std::max<u32>(1, n_seq));
+    u64 htotal = 0, cand_sum = 0;
+    for (u32 i = 0; i < n_seq; i++) {
+        u64 cs = 0;
+        for (u32 j = 0; j < nk; j++) cs += cnt[(size_t)i * nk + j];
+        cand_sum += cs;
+        u64 sz = 16;
+        while (sz < 2 * cs) sz <<= 1;
+        hoff[i] = htotal;
+        hsize[i] = sz;
+        htotal += sz;
+    }
+    dev_buf d_hoff, d_hsize, d_keys, d_rows, d_sorted, d_scratch;
+    if ((rc = d_hoff.alloc(hoff.size() * 8)) || (rc = d_hsize.alloc(hsize.size() * 8)) || (rc = d_keys.alloc(htotal * 16)) ||
+        (rc = d_rows.alloc(cand_sum * sizeof(prf_ihit_dev))) || (rc = d_sorted.alloc(cand_sum * sizeof(prf_ihit_dev))) ||
+        (rc = d_scratch.alloc(prf_int_sort_scratch_bytes(cand_sum))))
+        return rc;
+    HIPCHK(hipMemcpyAsync(d_hoff.p, hoff.data(), hoff.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_hsize.p, hsize.data(), hsize.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_keys.p, 0, htotal * 16, st));
+    HIPCHK(hipMemsetAsync((u64 *)d_ctr.p + 5, 0, 8, st));
+    HIPCHK(hipEventRecord(c->ev[2], st));
+    HIPCHK(prf_launch_int_emit(st, (const prf_ilane *)d_lanes.p, nk, n_seq, (const prf_icand *)d_cands.p, (const u64 *)d_cnt.p,
+                               (const u64 *)d_fl.p, (const u64 *)d_hoff.p, (const u64 *)d_hsize.p, (u64 *)d_keys.p,
+                               (prf_ihit_dev *)d_rows.p, (u64 *)d_ctr.p + 5));
+    launches++;
+    u64 n_rows = 0;
+    HIPCHK(hipMemcpyAsync(&n_rows, (u64 *)d_ctr.p + 5, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (n_rows > cand_sum) return fail(PRF_EHIP, "prf_scan_interrupted: emission returned %llu rows for %llu candidates",
+                                       (unsigned long long)n_rows, (unsigned long long)cand_sum);
+    HIPCHK(prf_int_sort_rows(st, (const prf_ihit_dev *)d_rows.p, n_rows, (prf_ihit_dev *)d_sorted.p, d_scratch.p));
+    if (n_rows) launches += 11;
+    HIPCHK(hipEventRecord(c->ev[3], st));
+    prf_ihit *rows = nullptr;
+    if (out && n_rows) {
+        rows = (prf_ihit *)malloc(n_rows * sizeof(prf_ihit));
+        if (!rows) return fail(PRF_ENOMEM, "prf_scan_interrupted: cannot allocate %llu rows", (unsigned long long)n_rows);
+        const hipError_t e = hipMemcpyAsync(rows, d_sorted.p, n_rows * sizeof(prf_ihit), hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) { free(rows); HIPCHK(e); }
+    }
+    {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { free(rows); HIPCHK(e); }
+    }
+    float all_ms = 0, emit_ms = 0;
+    HIPCHK(hipEventElapsedTime(&all_ms, c->ev[0], c->ev[3]));
+    HIPCHK(hipEventElapsedTime(&emit_ms, c->ev[2], c->ev[3]));
+    c->last.nhits = 0;  // the rows of this lane are handed over on the host only
+    c->last.rows = nullptr;
+    if (out) { out->rows = rows; out->n = rows ? n_rows : 0; }
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        stats->scan_ms = all_ms;
+        stats->phase1_ms = walk_ms;
+        stats->phase2_ms = emit_ms;
+        stats->positions = positions;
+        stats->packed_bytes = positions;  // this lane reads the bytes themselves
+        stats->n_candidates = cand_sum;
+        stats->n_hits = n_rows;
+        stats->n_launches = launches;
+        stats->path = 3;
+        stats->sorted_on_device = 1;
+    }
+    if (counters_out) {
+        counters_out[0] = h_ctr[1];  // walk steps
+        counters_out[1] = h_ctr[2];  // memo lookups
+        counters_out[2] = h_ctr[3];  // memo hits
+        counters_out[3] = h_ctr[4];  // recorded episodes
+    }
+    return PRF_OK;
+}
+
+int prf_scan_interrupted_ex(prf_ctx *c, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax, uint32_t min_repeats,
+                            uint32_t min_span, uint32_t max_interruptions, uint32_t memo_stride, uint64_t memo_slots, prf_ihits *out,
+                            prf_scan_stats *stats, uint64_t *counters) {
+    return guarded("prf_scan_interrupted", [&] {
+        return interrupted_impl(c, contigs, n_contigs, kmin, kmax, min_repeats, min_span, max_interruptions, memo_stride, memo_slots, out,
+                                stats, counters);
+    });
+}
+
+int prf_scan_interrupted(prf_ctx *c, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax, uint32_t min_repeats,
+                         uint32_t min_span, uint32_t max_interruptions, prf_ihits *out, prf_scan_stats *stats) {
+    return prf_scan_interrupted_ex(c, contigs, n_contigs, kmin, kmax, min_repeats, min_span, max_interruptions, PRF_MEMO_STRIDE,
+                                   PRF_MEMO_SLOTS, out, stats, nullptr);
+}
+
+void prf_free_ihits(prf_ihits *hits) {
+    if (!hits) return;
+    free(hits->rows);
+    hits->rows = nullptr;
+    hits->n = 0;
+}
+
 // ---- pipelined scans: enqueue now, collect later (at most two in flight) ----
 // The launch latency and the host's share of a scan (~9 of ~37 us on the chr22 scan) then overlap the previous
 // scan's kernel: kernels of one stream run back to back.  Fused path only, no row sink, buffers already sized by an

@@ -59,3 +59,36 @@ hipError_t prf_launch_lit_unpack(hipStream_t s, const u64 *H, const u64 *L, cons
 // the rows of the event kernel sorted by (start, end) and reduced to the shortest motif per (start, end), on the device
 hipError_t prf_lit_sort_unique(hipStream_t s, const prf_hit_dev *rows, u64 n, prf_hit_dev *out, u64 *n_out, void **scratch,
                                size_t *scratch_bytes);
+
+// interrupted repeats (scan_interrupted.hip), one lane per (sequence, motif size) -- DESIGN 9
+struct prf_ilane {
+    u64 seq_base;             // byte offset of the (upper-cased, untrimmed) sequence in the buffer, 16-byte aligned
+    u64 cand_off, cand_cap;   // the lane's candidate list
+    u64 memo_off, memo_slots; // its memo table (memo_slots == 0: no memo)
+    u64 ep_off, ep_cap;       // its episode outcome words (episodes past ep_cap are not recorded)
+    u32 seq, k;
+};
+struct prf_icand {            // an output check that passed both span tests with no N in the motif
+    u64 start, end, mask;     // trimmed coordinates; mask: the phases allowed to vary
+    u32 homo, k;
+};
+struct prf_imemo {            // a state an episode passed through
+    u64 pos, mask, run;
+    u64 ep;                   // index of that episode's outcome word
+};
+struct prf_ihit_dev {         // = prf_ihit
+    u64 start, end;
+    u32 k, contig;
+    u64 nmask;
+};
+hipError_t prf_launch_int_trim(hipStream_t s, const uint8_t *buf, const u64 *seq_base, const u64 *chunks, u32 n_chunks,
+                               u64 *first_last);
+// counters[0..3] += steps, memo lookups, memo hits, recorded episodes
+hipError_t prf_launch_int_walk(hipStream_t s, const uint8_t *buf, const prf_ilane *lanes, u32 n_lanes, const u64 *first_last,
+                               u32 min_repeats, u32 min_span, u32 max_int, u32 stride, prf_icand *cands, u64 *cand_cnt,
+                               prf_imemo *memo, u32 *eps, u64 *counters);
+hipError_t prf_launch_int_emit(hipStream_t s, const prf_ilane *lanes, u32 nk, u32 n_seq, const prf_icand *cands, const u64 *cand_cnt,
+                               const u64 *first_last, const u64 *hash_off, const u64 *hash_size, u64 *keys, prf_ihit_dev *rows,
+                               u64 *row_cnt);
+size_t prf_int_sort_scratch_bytes(u64 n);
+hipError_t prf_int_sort_rows(hipStream_t s, const prf_ihit_dev *rows, u64 n, prf_ihit_dev *out, void *scratch);

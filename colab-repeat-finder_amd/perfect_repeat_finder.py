@@ -100,11 +100,45 @@ def _interval_cutoff(seq, fs, end_position):
     return n
 
 
+def _masked_motif(seq, start, k, nmask):
+    """The reference's final_motif (utils/repeat_tracker.py:207-209): seq[start:start+k] with N at the phases that vary."""
+    motif = seq[start:start + k].upper()
+    if nmask:
+        motif = "".join("N" if (nmask >> i) & 1 else ch for i, ch in enumerate(motif))
+    return motif
+
+
+def _interrupted_rows(seqs, fs, context=None):
+    """Interrupted repeats of whole sequences, all in one call (csrc/scan_interrupted.hip): numpy rows (start, end, k, contig,
+    nmask) sorted by (contig, start, end)."""
+    ctx = context or prf_native.default_context()
+    try:
+        rows, _stats = ctx.scan_interrupted(seqs, fs.min_motif_size, fs.max_motif_size, fs.min_repeats, fs.min_span,
+                                            fs.max_interruptions)
+    except prf_native.PrfError as exc:
+        if exc.code in (prf_native.PRF_EINVAL, prf_native.PRF_ESYMBOL, prf_native.PRF_EUNSUPPORTED):
+            raise ValueError(exc.message) from None
+        raise
+    return rows
+
+
 def detect_repeats(input_sequence, filter_settings, verbose=False, show_progress_bar=False, debug=False, context=None):
     """Detect perfect tandem repeats; see the module docstring.  `context` (a prf_native.Context) is an
-    extension: by default a process-wide context on device PRF_DEVICE / LOCAL_RANK / 0 is used."""
+    extension: by default a process-wide context on device PRF_DEVICE / LOCAL_RANK / 0 is used.
+    filter_settings.max_interruptions > 0 (an extension, the reference's RepeatTracker): interrupted repeats of the whole
+    sequence by the driver of DESIGN 9; the motif has N at the phases allowed to vary."""
     _check_settings(filter_settings)
     fs = filter_settings
+    max_int = getattr(fs, "max_interruptions", 0) or 0
+    if max_int < 0:
+        raise ValueError(f"max_interruptions is set to {max_int}. It must be at least 0.")
+    if max_int > 0:
+        if hasattr(fs, "interval_start_0based") or hasattr(fs, "interval_end"):
+            raise ValueError("interval mode is not supported with max_interruptions > 0: the lock-step loop's stopping rule is "
+                             "undefined for a tracker that jumps back; scan the whole sequence")
+        rows = _interrupted_rows([_to_ascii(input_sequence)], fs, context)
+        return [(int(r["start"]), int(r["end"]), _masked_motif(input_sequence, int(r["start"]), int(r["k"]), int(r["nmask"])))
+                for r in rows]
     has_interval = hasattr(fs, "interval_start_0based") or hasattr(fs, "interval_end")
     if not has_interval and fs.min_repeats >= 2:
         # no interval: N-trimming is a no-op on the rows (N never matches), SURVEY 3.4
@@ -163,6 +197,9 @@ def _build_parser():
     g.add_argument("-max", "--max-motif-size", type=int, default=50, help="Largest motif size (bp).")
     g.add_argument("--min-repeats", type=int, default=3, help="Fewest copies of the motif a repeat must have.")
     g.add_argument("--min-span", type=int, default=9, help="Fewest consecutive bases a repeat must cover.")
+    g.add_argument("--max-interruptions", type=int, default=0,
+                   help="(the reference's RepeatTracker) how many positions within the motif may vary across repeats; 0: perfect "
+                        "repeats only.  Whole sequences only (no --interval), min repeats >= 2, max motif size <= 64.")
     p.add_argument("-i", "--interval", help="Restrict the scan to chrom:start_0based-end.")
     p.add_argument("-p", "--plot", help="Accepted for compatibility; plotting is not part of this build.")
     p.add_argument("-o", "--output-prefix", help="Prefix of the output TSV (and BED, for FASTA input).")
@@ -343,10 +380,40 @@ def _scan_whole_fasta_sharded(path, bed_path, fs, report, scan_fn=None):
             dist.destroy_process_group()
 
 
+def _scan_fasta_interrupted(args, bed_path):
+    """--max-interruptions > 0: every record of the FASTA in one launch; BED lines with the masked motif."""
+    fasta = prf_native.Fasta(args.input_sequence)     # holds the records' native memory until the rows are written
+    entries = list(fasta)
+    _check_settings(args)
+    rows = _interrupted_rows([(e.addr, e.length) for e in entries], args)
+    import numpy as np
+    counts = np.bincount(rows["contig"], minlength=len(entries)) if len(rows) else np.zeros(len(entries), dtype=np.int64)
+    with open(bed_path, "wt") as bed:
+        at = 0
+        for ci, (e, n_rows) in enumerate(zip(entries, counts)):
+            print(f"Processing {e.name} ({len(e):,d} bp)")
+            seq = e.seq if n_rows else ""
+            part = rows[at:at + int(n_rows)]
+            at += int(n_rows)
+            bed.writelines(f"{e.name}\t{int(r['start'])}\t{int(r['end'])}\t{_masked_motif(seq, int(r['start']), int(r['k']), int(r['nmask']))}\n"
+                           for r in part)
+            print(f"Found {int(n_rows):,d} repeats")
+    fasta.close()
+    print(f"Wrote results to {bed_path}")
+
+
 def _scan_fasta(args, parser):
     if not args.output_prefix:
         args.output_prefix = re.sub(".fa(sta)?(.gz)?", "", args.input_sequence)   # same unanchored pattern as reference :114
     bed_path = f"{os.path.basename(args.output_prefix)}.bed"
+    if args.max_interruptions > 0:
+        if args.interval:
+            parser.error("--interval is not supported with --max-interruptions > 0 (the lock-step loop's stopping rule is undefined "
+                         "for a tracker that jumps back): scan whole records")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--max-interruptions > 0 runs in one process (one launch for all records); it is not sharded over ranks")
+        _scan_fasta_interrupted(args, bed_path)
+        return
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch  # noqa: F401  before libprf.so is loaded: PyTorch brings its own HIP runtime (INTEGRATION.md, load order)
     if not args.interval:
@@ -420,6 +487,8 @@ def main(argv=None):
         parser.error(f"--min-repeats is set to {args.min_repeats}. It must be at least 1.")
     if args.min_span < 1:
         parser.error(f"--min-span is set to {args.min_span}. It must be at least 1.")
+    if args.max_interruptions < 0:
+        parser.error(f"--max-interruptions is set to {args.max_interruptions}. It must be at least 0.")
     if os.path.isfile(args.input_sequence):
         _scan_fasta(args, parser)
     elif set(args.input_sequence.upper()) <= set("ACGTN"):

@@ -50,6 +50,20 @@ class _Hits(ctypes.Structure):
     _fields_ = [("rows", ctypes.POINTER(_Hit)), ("n", ctypes.c_uint64)]
 
 
+class _IHit(ctypes.Structure):
+    _fields_ = [("start", ctypes.c_uint64), ("end", ctypes.c_uint64), ("k", ctypes.c_uint32), ("contig", ctypes.c_uint32),
+                ("nmask", ctypes.c_uint64)]
+
+
+class _IHits(ctypes.Structure):
+    _fields_ = [("rows", ctypes.POINTER(_IHit)), ("n", ctypes.c_uint64)]
+
+
+IHIT_DTYPE = [("start", "<u8"), ("end", "<u8"), ("k", "<u4"), ("contig", "<u4"), ("nmask", "<u8")]
+MEMO_STRIDE = 8
+MEMO_SLOTS = 1 << 22
+
+
 class ScanStats(ctypes.Structure):
     _fields_ = [("scan_ms", ctypes.c_double), ("phase1_ms", ctypes.c_double), ("phase2_ms", ctypes.c_double),
                 ("positions", ctypes.c_uint64), ("packed_bytes", ctypes.c_uint64), ("n_candidates", ctypes.c_uint64),
@@ -66,7 +80,7 @@ EXPORTS = ["prf_abi_version", "prf_device_count", "prf_last_error", "prf_open", 
            "prf_fasta_entry", "prf_fasta_close", "prf_write_bed", "prf_write_tsv", "prf_genome_synth", "prf_scan_timings", "prf_set_row_sink", "prf_fasta_open_contig", "prf_scan_genome_async",
            "prf_scan_wait", "prf_genome_standin", "prf_genome_select", "prf_genome_tile_classes", "prf_tile_positions", "prf_scan_timings_split", "prf_last_hits_packed_to_device",
            "prf_genome_contig_bases", "prf_scan_literal", "prf_scan_genome_async_packed", "prf_stream_wait_for",
-           "prf_genome_footprint"]
+           "prf_genome_footprint", "prf_scan_interrupted", "prf_scan_interrupted_ex", "prf_free_ihits"]
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -134,6 +148,12 @@ def load_library():
         lib.prf_scan_literal.argtypes = [vp, ctypes.POINTER(_Contig), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                          ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(_Hits), ctypes.POINTER(ScanStats)]
         lib.prf_free_hits.argtypes = [ctypes.POINTER(_Hits)]
+        lib.prf_scan_interrupted.argtypes = [vp, ctypes.POINTER(_Contig), ctypes.c_int] + [ctypes.c_uint32] * 5 + [
+            ctypes.POINTER(_IHits), ctypes.POINTER(ScanStats)]
+        lib.prf_scan_interrupted_ex.argtypes = [vp, ctypes.POINTER(_Contig), ctypes.c_int] + [ctypes.c_uint32] * 6 + [
+            ctypes.c_uint64, ctypes.POINTER(_IHits), ctypes.POINTER(ScanStats), ctypes.POINTER(ctypes.c_uint64)]
+        lib.prf_free_ihits.argtypes = [ctypes.POINTER(_IHits)]
+        lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
         lib.prf_measure_hbm_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
         lib.prf_last_hits_to_device.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
@@ -332,6 +352,33 @@ class Context:
             return _rows(hits), stats
         finally:
             self.lib.prf_free_hits(ctypes.byref(hits))
+
+    def scan_interrupted(self, seqs, kmin, kmax, min_repeats, min_span, max_interruptions, memo_stride=None, memo_slots=None,
+                         counters=False):
+        """Interrupted repeats of many whole sequences in one call (prf_scan_interrupted): (rows, stats[, counters]).  rows: numpy
+        records (start, end, k, contig, nmask) sorted by (contig, start, end); bit i of nmask = phase i of the motif may vary.
+        memo_stride / memo_slots: the walk's memo table (the rows do not depend on it); counters: also return a dict of the
+        walk's steps, memo lookups, memo hits and recorded episodes."""
+        import numpy as np
+        arr, _keep = _contig_array(list(seqs))
+        hits, stats = _IHits(), ScanStats()
+        ctr = (ctypes.c_uint64 * 4)()
+        _check(self.lib, self.lib.prf_scan_interrupted_ex(
+            self._h, arr, len(seqs), kmin, kmax, min_repeats, min_span, max_interruptions,
+            MEMO_STRIDE if memo_stride is None else memo_stride, MEMO_SLOTS if memo_slots is None else memo_slots,
+            ctypes.byref(hits), ctypes.byref(stats), ctr))
+        try:
+            n = hits.n
+            if n == 0:
+                rows = np.zeros(0, dtype=IHIT_DTYPE)
+            else:
+                buf = np.ctypeslib.as_array(ctypes.cast(hits.rows, ctypes.POINTER(ctypes.c_uint8)), shape=(n * ctypes.sizeof(_IHit),))
+                rows = buf.view(np.dtype(IHIT_DTYPE)).copy()
+        finally:
+            self.lib.prf_free_ihits(ctypes.byref(hits))
+        if counters:
+            return rows, stats, {"steps": ctr[0], "lookups": ctr[1], "hits": ctr[2], "episodes": ctr[3]}
+        return rows, stats
 
     def scan_literal(self, seq, kmin, kmax, min_repeats, min_span, stop=None):
         """The literal lane on one sequence (prf_scan_literal); stop: lock-step iterations performed, default all."""

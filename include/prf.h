@@ -82,7 +82,7 @@ typedef struct prf_scan_stats {
     uint64_t n_candidates;  /* phase-1 candidates                                                        */
     uint64_t n_hits;        /* rows                                                                      */
     uint32_t n_launches;    /* kernel launches in the timed region                                       */
-    uint32_t path;          /* 0 = generic kernel, 1 = vertical bit-sliced kernel, 2 = literal lane      */
+    uint32_t path;          /* 0 = generic kernel, 1 = vertical bit-sliced kernel, 2 = literal lane, 3 = interrupted */
     uint64_t seq;           /* fused path: serial number of this scan on its context (prf_scan_timings)  */
     uint32_t sorted_on_device; /* 1: the rows left the device sorted by (contig, start, end), no host sort   */
     uint32_t tiles_launched;   /* fused path: 65536-position tiles scanned (tiles of nothing but N are skipped)     */
@@ -169,6 +169,42 @@ int prf_scan(prf_ctx *ctx, const prf_contig *contigs, int n_contigs, uint32_t km
  * N-trimming here (reference perfect_repeat_finder.py:40-46 is the caller's; prf_scan does it for min_repeats == 1). */
 int prf_scan_literal(prf_ctx *ctx, const prf_contig *contig, uint32_t kmin, uint32_t kmax, uint32_t min_repeats,
                      uint32_t min_span, uint64_t stop, prf_hits *out, prf_scan_stats *stats);
+
+/* ---- interrupted repeats: the reference's RepeatTracker with max_interruptions > 0 (utils/repeat_tracker.py) ----
+ * The reference has no driver for that class; the one this library implements: every contig upper-cased and trimmed
+ * of the N at both ends (reference perfect_repeat_finder.py:33-46), then one RepeatTracker per motif size k = kmin .. kmax, in
+ * ascending order, over the trimmed contig, all writing ONE (start, end) -> motif dictionary of that contig; each tracker runs
+ * `while t.advance(): pass; t.done()`.  Rows are the dictionary sorted by (start, end), shifted by the trimmed head; the motif
+ * is seq.upper()[start:start+k] with N at the phases set in nmask (the reference's final_motif).  Whole contigs, many per call;
+ * min_repeats >= 2 and kmax <= 64 (PRF_EUNSUPPORTED otherwise), max_interruptions >= 1 (0 is prf_scan's perfect path:
+ * PRF_EINVAL), PRF_ESYMBOL for a byte that is not a letter.  Rows sorted by (contig, start, end) on the device.
+ * Stats: path = 3, phase1_ms = the walk kernel, phase2_ms = emission and sort. */
+typedef struct prf_ihit {
+    uint64_t start;  /* 0-based, contig-local      */
+    uint64_t end;    /* exclusive                  */
+    uint32_t k;      /* motif size                 */
+    uint32_t contig; /* index into the contigs array */
+    uint64_t nmask;  /* bit i: phase i of the motif may vary (an N in the motif text) */
+} prf_ihit;
+
+typedef struct prf_ihits {
+    prf_ihit *rows; /* library-owned; free with prf_free_ihits */
+    uint64_t n;
+} prf_ihits;
+
+#define PRF_MEMO_STRIDE 8u          /* prf_scan_interrupted: a state is recorded every 8 positions ...          */
+#define PRF_MEMO_SLOTS (1ull << 22) /* ... in a table of at most this many records per (contig, motif size)     */
+
+int prf_scan_interrupted(prf_ctx *ctx, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax,
+                         uint32_t min_repeats, uint32_t min_span, uint32_t max_interruptions, prf_ihits *out,
+                         prf_scan_stats *stats);
+/* The same with the walk's memo table chosen by the caller (memo_stride: a power of two, 0 = no memo; memo_slots: records per
+ * (contig, motif size), 0 = no memo) -- the rows do not depend on either.  counters (may be NULL) receives four words: walk
+ * steps (tracker moves), memo lookups, memo hits, recorded episodes. */
+int prf_scan_interrupted_ex(prf_ctx *ctx, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax,
+                            uint32_t min_repeats, uint32_t min_span, uint32_t max_interruptions, uint32_t memo_stride,
+                            uint64_t memo_slots, prf_ihits *out, prf_scan_stats *stats, uint64_t *counters);
+void prf_free_ihits(prf_ihits *hits);
 
 /* Pipelined scans.  prf_scan_genome_async() enqueues a scan and returns its serial number at once;
  * prf_scan_wait() collects it (row count and candidate count in *stats; kernel time through prf_scan_timings;
