@@ -1138,10 +1138,16 @@ static int interrupted_check(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, 
 }
 
 static int interrupted_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs, u32 kmin, u32 kmax, u32 min_repeats, u32 min_span,
-                            u32 max_int, u32 memo_stride, u64 memo_slots, prf_ihits *out, prf_scan_stats *stats, uint64_t *counters_out) {
+                            u32 max_int, u32 memo_stride, u64 memo_slots, u64 chunk, prf_ihits *out, prf_scan_stats *stats,
+                            uint64_t *counters_out) {
+    // chunk == 0: one lane per (sequence, k), one lane per thread (prf_scan_interrupted_ex).  Otherwise the landings of each
+    // (sequence, k) are cut into chunks of `chunk` positions, one lane per wave, and counters_out has six words.
     if (out) { out->rows = nullptr; out->n = 0; }
     int rc = interrupted_check(kmin, kmax, min_repeats, min_span, max_int, memo_stride);
     if (rc) return rc;
+    if (chunk && chunk < PRF_INT_CHUNK_MIN)
+        return fail(PRF_EINVAL, "prf_scan_interrupted_chunked: chunk %llu is below the minimum of %u positions (0 = one lane per motif size)",
+                    (unsigned long long)chunk, (unsigned)PRF_INT_CHUNK_MIN);
     if (!c) return fail(PRF_EINVAL, "prf_scan_interrupted: NULL context");
     if (n_contigs < 0 || (n_contigs && !contigs)) return fail(PRF_EINVAL, "prf_scan_interrupted: bad contig array");
     for (int i = 0; i < n_contigs; i++) {
@@ -1151,11 +1157,9 @@ static int interrupted_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs
     if (c->slot[0].seq || c->slot[1].seq) return fail(PRF_EINVAL, "prf_scan_interrupted: pipelined scans are in flight on this context");
     HIPCHK(hipSetDevice(c->dev));
     const u32 nk = kmax - kmin + 1, n_seq = (u32)n_contigs;
-    const u64 n_lanes64 = (u64)n_seq * nk;
-    if (n_lanes64 > 0x7fffffffull) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: too many (sequence, motif size) lanes");
-    const u32 n_lanes = (u32)n_lanes64;
+    if ((u64)n_seq * nk > 0x7fffffffull) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: too many (sequence, motif size) lanes");
 
-    // host plan: sequence placement (16-byte aligned, 16 readable bytes behind each), trim chunks, lanes
+    // host plan: sequence placement (16-byte aligned, 16 readable bytes behind each), trim chunks
     std::vector<u64> seq_base(std::max<u32>(1, n_seq)), chunks;
     u64 total = 0, positions = 0;
     for (u32 i = 0; i < n_seq; i++) {
@@ -1169,31 +1173,10 @@ static int interrupted_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs
         }
     }
     const u32 n_chunks = (u32)(chunks.size() / 3);
-    std::vector<prf_ilane> lanes(std::max<u32>(1, n_lanes));
-    std::vector<u64> cand_cap(n_lanes);
-    // about one candidate per five positions on random sequence (every episode that jumps back ends in one): room for one per
-    // four, so that the walk usually runs once
-    for (u32 li = 0; li < n_lanes; li++) cand_cap[li] = contigs[li / nk].len / 4 + 16;
-    u64 memo_total = 0, ep_total = 0;
-    for (u32 li = 0; li < n_lanes; li++) {
-        prf_ilane &ln = lanes[li];
-        const u64 len = contigs[li / nk].len;
-        ln.seq = li / nk;
-        ln.k = kmin + li % nk;
-        ln.seq_base = seq_base[ln.seq];
-        ln.memo_slots = memo_stride ? std::min<u64>(memo_slots, len / memo_stride + 1) : 0;
-        ln.memo_off = memo_total;
-        memo_total += ln.memo_slots;
-        ln.ep_cap = ln.memo_slots ? len / 4 + 64 : 0;  // episodes land at strictly increasing positions: at most len of them
-        ln.ep_off = ep_total;
-        ep_total += ln.ep_cap;
-    }
 
-    dev_buf d_seq, d_base, d_chunks, d_fl, d_lanes, d_cands, d_cnt, d_memo, d_eps, d_ctr;
+    dev_buf d_seq, d_base, d_chunks, d_fl, d_lanes, d_cands, d_cnt, d_end, d_first_end, d_bcount, d_memo, d_eps, d_ctr;
     if ((rc = d_seq.alloc(total + 16)) || (rc = d_base.alloc(seq_base.size() * 8)) || (rc = d_chunks.alloc(chunks.size() * 8)) ||
-        (rc = d_fl.alloc(2 * 8 * (size_t)std::max<u32>(1, n_seq))) || (rc = d_lanes.alloc(lanes.size() * sizeof(prf_ilane))) ||
-        (rc = d_cnt.alloc(8 * (size_t)std::max<u32>(1, n_lanes))) || (rc = d_memo.alloc(memo_total * sizeof(prf_imemo))) ||
-        (rc = d_eps.alloc(ep_total * 4)) || (rc = d_ctr.alloc(8 * 8)))
+        (rc = d_fl.alloc(2 * 8 * (size_t)std::max<u32>(1, n_seq))) || (rc = d_ctr.alloc(8 * 8)))
         return rc;
     hipStream_t st = c->stream;
     HIPCHK(hipMemsetAsync(d_seq.p, 'N', total + 16, st));  // the gaps are letters: the symbol check passes over them
@@ -1213,6 +1196,7 @@ static int interrupted_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs
     launches += 2;
     u64 h_ctr[8];
     HIPCHK(hipMemcpyAsync(h_ctr, d_ctr.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(fl.data(), d_fl.p, fl.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (h_ctr[0] != ~0ull) {
         const u64 at = h_ctr[0];
@@ -1221,7 +1205,71 @@ static int interrupted_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs
                     "ordinary symbols, like the reference -- any other letter, in either case)", ci, (unsigned long long)(at - seq_base[ci]));
     }
 
+    // lanes in (sequence, k, chunk) order; the chunks cut the trimmed sequence
+    std::vector<u32> lane0(std::max<u32>(1, n_seq)), nch(std::max<u32>(1, n_seq));
+    u64 n_lanes64 = 0;
+    for (u32 i = 0; i < n_seq; i++) {
+        const u64 n_trim = fl[2 * i] == ~0ull ? 0 : fl[2 * i + 1] - fl[2 * i];
+        const u64 nc = chunk ? std::max<u64>(1, (n_trim + chunk - 1) / chunk) : 1;
+        if (n_lanes64 + nc * nk > 0x7fffffffull) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: too many (sequence, motif size, chunk) lanes");
+        lane0[i] = (u32)n_lanes64;
+        nch[i] = (u32)nc;
+        n_lanes64 += nc * nk;
+    }
+    const u32 n_lanes = (u32)n_lanes64;
+    std::vector<prf_ilane> lanes(std::max<u32>(1, n_lanes));
+    std::vector<u64> cand_cap(n_lanes);
+    u64 memo_total = 0;
+    for (u32 i = 0, li = 0; i < n_seq; i++) {
+        const u64 len = contigs[i].len, reach = chunk ? std::min<u64>(len, chunk) : len;
+        for (u32 j = 0; j < nk; j++)
+            for (u32 ch = 0; ch < nch[i]; ch++, li++) {
+                prf_ilane &ln = lanes[li];
+                ln.seq = i;
+                ln.k = kmin + j;
+                ln.seq_base = seq_base[i];
+                ln.chunk = ch;
+                ln.kslot = i * nk + j;
+                ln.lo = (u64)ch * chunk;
+                ln.hi = chunk ? (u64)(ch + 1) * chunk : (u64)INT64_MAX;
+                ln.cand_off = ln.cand_cap = ln.ep_off = ln.ep_cap = 0;
+                ln.memo_slots = memo_stride ? std::min<u64>(memo_slots, reach / memo_stride + 1) : 0;
+                ln.memo_off = memo_total;
+                memo_total += ln.memo_slots;
+            }
+    }
+    if ((rc = d_lanes.alloc(lanes.size() * sizeof(prf_ilane))) || (rc = d_cnt.alloc(8 * (size_t)std::max<u32>(1, n_lanes))) ||
+        (rc = d_end.alloc(4 * (size_t)std::max<u32>(1, n_lanes))) || (rc = d_first_end.alloc(4 * (size_t)std::max<u32>(1, n_seq * nk))) ||
+        (rc = d_memo.alloc(memo_total * sizeof(prf_imemo))))
+        return rc;
+    if (chunk) {
+        // every episode of a lane lands on a boundary of its chunk (the first lane's first one on position 0) and lists at most
+        // one candidate: counting the boundaries sizes both arrays so that the walk runs once
+        if ((rc = d_bcount.alloc(8 * (size_t)std::max<u32>(1, n_lanes)))) return rc;
+        HIPCHK(hipMemcpyAsync(d_lanes.p, lanes.data(), lanes.size() * sizeof(prf_ilane), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(d_bcount.p, 0, 8 * (size_t)std::max<u32>(1, n_lanes), st));
+        HIPCHK(prf_launch_int_bound(st, (const uint8_t *)d_seq.p, (const prf_ilane *)d_lanes.p, n_lanes, (const u64 *)d_fl.p, (u64 *)d_bcount.p));
+        launches++;
+        if (n_lanes) HIPCHK(hipMemcpyAsync(cand_cap.data(), d_bcount.p, 8 * (size_t)n_lanes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (u32 li = 0; li < n_lanes; li++) cand_cap[li] += 1;
+    } else {
+        // about one candidate per five positions on random sequence (every episode that jumps back ends in one): room for one per
+        // four, so that the walk usually runs once
+        for (u32 li = 0; li < n_lanes; li++) cand_cap[li] = contigs[lanes[li].seq].len / 4 + 16;
+    }
+    u64 ep_total = 0;
+    for (u32 li = 0; li < n_lanes; li++) {
+        prf_ilane &ln = lanes[li];
+        // episodes land at strictly increasing positions: at most len of them; past ep_cap they are not recorded
+        ln.ep_cap = !ln.memo_slots ? 0 : chunk ? cand_cap[li] : contigs[ln.seq].len / 4 + 64;
+        ln.ep_off = ep_total;
+        ep_total += ln.ep_cap;
+    }
+    if ((rc = d_eps.alloc(ep_total * 4))) return rc;
+
     std::vector<u64> cnt(std::max<u32>(1, n_lanes));
+    std::vector<u32> lane_end(std::max<u32>(1, n_lanes));
     for (int attempt = 0;; attempt++) {
         u64 cand_total = 0;
         for (u32 li = 0; li < n_lanes; li++) {
@@ -1232,14 +1280,16 @@ static int interrupted_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs
         if ((rc = d_cands.alloc(cand_total * sizeof(prf_icand)))) return rc;
         HIPCHK(hipMemcpyAsync(d_lanes.p, lanes.data(), lanes.size() * sizeof(prf_ilane), hipMemcpyHostToDevice, st));
         if (memo_total) HIPCHK(hipMemsetAsync(d_memo.p, 0xFF, memo_total * sizeof(prf_imemo), st));  // no state has pos ~0
+        HIPCHK(hipMemsetAsync(d_first_end.p, 0xFF, 4 * (size_t)std::max<u32>(1, n_seq * nk), st));
         HIPCHK(hipMemsetAsync((u64 *)d_ctr.p + 1, 0, 7 * 8, st));
         HIPCHK(hipEventRecord(c->ev[1], st));
         HIPCHK(prf_launch_int_walk(st, (const uint8_t *)d_seq.p, (const prf_ilane *)d_lanes.p, n_lanes, (const u64 *)d_fl.p, min_repeats,
-                                   min_span, max_int, memo_stride, (prf_icand *)d_cands.p, (u64 *)d_cnt.p, (prf_imemo *)d_memo.p,
-                                   (u32 *)d_eps.p, (u64 *)d_ctr.p + 1));
+                                   min_span, max_int, memo_stride, (prf_icand *)d_cands.p, (u64 *)d_cnt.p, (u32 *)d_end.p,
+                                   chunk ? (u32 *)d_first_end.p : nullptr, (prf_imemo *)d_memo.p, (u32 *)d_eps.p, (u64 *)d_ctr.p + 1));
         HIPCHK(hipEventRecord(c->ev[2], st));
         launches++;
         HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, 8 * (size_t)n_lanes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(lane_end.data(), d_end.p, 4 * (size_t)n_lanes, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(h_ctr, d_ctr.p, 8 * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         bool over = false;
@@ -1250,6 +1300,17 @@ static int interrupted_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs
         if (!over) break;
         if (attempt >= 1) return fail(PRF_EHIP, "prf_scan_interrupted: the candidate counts changed between two runs");
     }
+    // the chunks behind the first lane of a (sequence, k) that ended start on landings the walk never reaches: dropped
+    u64 dropped = 0;
+    for (u32 i = 0; i < n_seq; i++)
+        for (u32 j = 0; j < nk; j++) {
+            const u32 l0 = lane0[i] + j * nch[i];
+            u32 e = 0;
+            while (e < nch[i] && !lane_end[l0 + e]) e++;
+            if (e == nch[i]) return fail(PRF_EHIP, "prf_scan_interrupted: no lane of contig %u, motif size %u reached the end", i, kmin + j);
+            for (u32 ch = e + 1; ch < nch[i]; ch++) cnt[l0 + ch] = 0;
+            dropped += nch[i] - 1 - e;
+        }
     float walk_ms = 0;
     HIPCHK(hipEventElapsedTime(&walk_ms, c->ev[1], c->ev[2]));
 
@@ -1258,7 +1319,7 @@ static int interrupted_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs
     u64 htotal = 0, cand_sum = 0;
     for (u32 i = 0; i < n_seq; i++) {
         u64 cs = 0;
-        for (u32 j = 0; j < nk; j++) cs += cnt[(size_t)i * nk + j];
+        for (u32 l = 0; l < nk * nch[i]; l++) cs += cnt[(size_t)lane0[i] + l];
         cand_sum += cs;
         u64 sz = 16;
         while (sz < 2 * cs) sz <<= 1;
@@ -1266,17 +1327,20 @@ static int interrupted_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs
         hsize[i] = sz;
         htotal += sz;
     }
-    dev_buf d_hoff, d_hsize, d_keys, d_rows, d_sorted, d_scratch;
-    if ((rc = d_hoff.alloc(hoff.size() * 8)) || (rc = d_hsize.alloc(hsize.size() * 8)) || (rc = d_keys.alloc(htotal * 16)) ||
+    dev_buf d_hoff, d_hsize, d_keys, d_rows, d_sorted, d_scratch, d_lane0, d_nch;
+    if ((rc = d_lane0.alloc(lane0.size() * 4)) || (rc = d_nch.alloc(nch.size() * 4)) || (rc = d_hoff.alloc(hoff.size() * 8)) || (rc = d_hsize.alloc(hsize.size() * 8)) || (rc = d_keys.alloc(htotal * 16)) ||
         (rc = d_rows.alloc(cand_sum * sizeof(prf_ihit_dev))) || (rc = d_sorted.alloc(cand_sum * sizeof(prf_ihit_dev))) ||
         (rc = d_scratch.alloc(prf_int_sort_scratch_bytes(cand_sum))))
         return rc;
+    HIPCHK(hipMemcpyAsync(d_lane0.p, lane0.data(), lane0.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_nch.p, nch.data(), nch.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_hoff.p, hoff.data(), hoff.size() * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_hsize.p, hsize.data(), hsize.size() * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_keys.p, 0, htotal * 16, st));
     HIPCHK(hipMemsetAsync((u64 *)d_ctr.p + 5, 0, 8, st));
     HIPCHK(hipEventRecord(c->ev[2], st));
-    HIPCHK(prf_launch_int_emit(st, (const prf_ilane *)d_lanes.p, nk, n_seq, (const prf_icand *)d_cands.p, (const u64 *)d_cnt.p,
+    HIPCHK(prf_launch_int_emit(st, (const prf_ilane *)d_lanes.p, nk, n_seq, (const u32 *)d_lane0.p, (const u32 *)d_nch.p,
+                               (const u32 *)d_end.p, (const prf_icand *)d_cands.p, (const u64 *)d_cnt.p,
                                (const u64 *)d_fl.p, (const u64 *)d_hoff.p, (const u64 *)d_hsize.p, (u64 *)d_keys.p,
                                (prf_ihit_dev *)d_rows.p, (u64 *)d_ctr.p + 5));
     launches++;
@@ -1323,6 +1387,10 @@ static int interrupted_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs
         counters_out[1] = h_ctr[2];  // memo lookups
         counters_out[2] = h_ctr[3];  // memo hits
         counters_out[3] = h_ctr[4];  // recorded episodes
+        if (chunk) {
+            counters_out[4] = n_lanes;
+            counters_out[5] = dropped;
+        }
     }
     return PRF_OK;
 }
@@ -1331,15 +1399,27 @@ int prf_scan_interrupted_ex(prf_ctx *c, const prf_contig *contigs, int n_contigs
                             uint32_t min_span, uint32_t max_interruptions, uint32_t memo_stride, uint64_t memo_slots, prf_ihits *out,
                             prf_scan_stats *stats, uint64_t *counters) {
     return guarded("prf_scan_interrupted", [&] {
-        return interrupted_impl(c, contigs, n_contigs, kmin, kmax, min_repeats, min_span, max_interruptions, memo_stride, memo_slots, out,
-                                stats, counters);
+        return interrupted_impl(c, contigs, n_contigs, kmin, kmax, min_repeats, min_span, max_interruptions, memo_stride, memo_slots, 0,
+                                out, stats, counters);
+    });
+}
+
+int prf_scan_interrupted_chunked(prf_ctx *c, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax, uint32_t min_repeats,
+                                 uint32_t min_span, uint32_t max_interruptions, uint32_t memo_stride, uint64_t memo_slots, uint64_t chunk,
+                                 prf_ihits *out, prf_scan_stats *stats, uint64_t *counters) {
+    return guarded("prf_scan_interrupted_chunked", [&] {
+        if (counters && !chunk) counters[4] = counters[5] = 0;
+        const int rc = interrupted_impl(c, contigs, n_contigs, kmin, kmax, min_repeats, min_span, max_interruptions, memo_stride,
+                                        memo_slots, chunk, out, stats, counters);
+        if (rc == PRF_OK && counters && !chunk) counters[4] = (uint64_t)n_contigs * (kmax - kmin + 1);  // one lane each, none dropped
+        return rc;
     });
 }
 
 int prf_scan_interrupted(prf_ctx *c, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax, uint32_t min_repeats,
                          uint32_t min_span, uint32_t max_interruptions, prf_ihits *out, prf_scan_stats *stats) {
-    return prf_scan_interrupted_ex(c, contigs, n_contigs, kmin, kmax, min_repeats, min_span, max_interruptions, PRF_MEMO_STRIDE,
-                                   PRF_MEMO_SLOTS, out, stats, nullptr);
+    return prf_scan_interrupted_chunked(c, contigs, n_contigs, kmin, kmax, min_repeats, min_span, max_interruptions, PRF_MEMO_STRIDE,
+                                        PRF_MEMO_SLOTS, PRF_INT_CHUNK, out, stats, nullptr);
 }
 
 void prf_free_ihits(prf_ihits *hits) {

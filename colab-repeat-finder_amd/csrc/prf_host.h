@@ -60,13 +60,15 @@ hipError_t prf_launch_lit_unpack(hipStream_t s, const u64 *H, const u64 *L, cons
 hipError_t prf_lit_sort_unique(hipStream_t s, const prf_hit_dev *rows, u64 n, prf_hit_dev *out, u64 *n_out, void **scratch,
                                size_t *scratch_bytes);
 
-// interrupted repeats (scan_interrupted.hip), one lane per (sequence, motif size) -- DESIGN 9
+// interrupted repeats (scan_interrupted.hip), one lane per (sequence, motif size, chunk of landing positions) -- DESIGN 9
 struct prf_ilane {
     u64 seq_base;             // byte offset of the (upper-cased, untrimmed) sequence in the buffer, 16-byte aligned
     u64 cand_off, cand_cap;   // the lane's candidate list
     u64 memo_off, memo_slots; // its memo table (memo_slots == 0: no memo)
     u64 ep_off, ep_cap;       // its episode outcome words (episodes past ep_cap are not recorded)
     u32 seq, k;
+    u64 lo, hi;               // the lane walks the episodes that land in [lo, hi) (trimmed positions); lo == 0: from position 0
+    u32 chunk, kslot;         // its chunk's number within (sequence, k); index of that (sequence, k)
 };
 struct prf_icand {            // an output check that passed both span tests with no N in the motif
     u64 start, end, mask;     // trimmed coordinates; mask: the phases allowed to vary
@@ -83,12 +85,17 @@ struct prf_ihit_dev {         // = prf_ihit
 };
 hipError_t prf_launch_int_trim(hipStream_t s, const uint8_t *buf, const u64 *seq_base, const u64 *chunks, u32 n_chunks,
                                u64 *first_last);
-// counters[0..3] += steps, memo lookups, memo hits, recorded episodes
+// counters[0..3] += steps, memo lookups, memo hits, recorded episodes; lane_end[li] = the walk ended in lane li.
+// first_end == NULL: one lane per thread (one chunk per (sequence, k)).  Otherwise one lane per wave, and first_end[kslot]
+// (set to ~0 by the caller) receives the first chunk of each (sequence, k) whose lane ended.
 hipError_t prf_launch_int_walk(hipStream_t s, const uint8_t *buf, const prf_ilane *lanes, u32 n_lanes, const u64 *first_last,
-                               u32 min_repeats, u32 min_span, u32 max_int, u32 stride, prf_icand *cands, u64 *cand_cnt,
-                               prf_imemo *memo, u32 *eps, u64 *counters);
-hipError_t prf_launch_int_emit(hipStream_t s, const prf_ilane *lanes, u32 nk, u32 n_seq, const prf_icand *cands, const u64 *cand_cnt,
-                               const u64 *first_last, const u64 *hash_off, const u64 *hash_size, u64 *keys, prf_ihit_dev *rows,
+                               u32 min_repeats, u32 min_span, u32 max_int, u32 stride, prf_icand *cands, u64 *cand_cnt, u32 *lane_end,
+                               u32 *first_end, prf_imemo *memo, u32 *eps, u64 *counters);
+// bcount[li] += the boundaries in lane li's [lo, hi): with one more for position 0, an upper bound of its episodes and candidates
+hipError_t prf_launch_int_bound(hipStream_t s, const uint8_t *buf, const prf_ilane *lanes, u32 n_lanes, const u64 *first_last,
+                                u64 *bcount);
+hipError_t prf_launch_int_emit(hipStream_t s, const prf_ilane *lanes, u32 nk, u32 n_seq, const u32 *lane0, const u32 *n_chunks,
+                               const u32 *lane_end, const prf_icand *cands, const u64 *cand_cnt, const u64 *first_last, const u64 *hash_off, const u64 *hash_size, u64 *keys, prf_ihit_dev *rows,
                                u64 *row_cnt);
 size_t prf_int_sort_scratch_bytes(u64 n);
 hipError_t prf_int_sort_rows(hipStream_t s, const prf_ihit_dev *rows, u64 n, prf_ihit_dev *out, void *scratch);

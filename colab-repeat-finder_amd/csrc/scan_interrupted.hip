@@ -2,9 +2,12 @@
 //
 // The tracker walks left to right but jumps back to its first interruption after every decision, so a literal replay walks
 // each position many times.  Its path does not depend on the shared dictionary or on its previous output, so the work splits:
-//   1. prf_int_walk_kernel, one lane per (sequence, k): the tracker's path, appending a candidate (start, end, phase mask,
-//      homopolymer) at every output check that passes both span tests with no N in the motif.  A memo table of states
-//      (position, run, phase set) recorded every `stride` positions lets an episode that meets a state an earlier episode
+//   1. the walk, one lane per (sequence, k, chunk of landing positions): the tracker's path, appending a candidate (start,
+//      end, phase mask, homopolymer) at every output check that passes both span tests with no N in the motif.  Every jump back
+//      lands clean on the next boundary (a mismatch right behind a match), so a lane that starts clean on the first
+//      boundary of its chunk and stops at the first landing behind it walks a piece of the whole walk.  prf_int_walk_kernel
+//      (one lane per thread, one chunk per (sequence, k)) and prf_int_walk_chunk_kernel (one lane per wave) share walk_lane().
+//      A memo table of states (position, run, phase set) recorded every `stride` positions lets an episode that meets a state an earlier episode
 //      passed through take that episode's outcome and jump at once (exact: inside an episode the path depends on the state
 //      only; the first interruption picks the jump target and nothing else).
 //   2. prf_int_emit_kernel, one lane per sequence: the dictionary (an open-addressing hash of (start, end)), the
@@ -44,13 +47,18 @@ __host__ __device__ __forceinline__ u64 memo_slot(u64 pos, u64 run, u64 mask, u6
     return (h >> 32) % slots;
 }
 
-__global__ void __launch_bounds__(64) prf_int_walk_kernel(const uint8_t *__restrict__ buf, const prf_ilane *__restrict__ lanes,
-                                                          u32 n_lanes, const u64 *__restrict__ first_last, u32 min_repeats,
-                                                          u32 min_span, u32 max_int, u32 stride, prf_icand *__restrict__ cands,
-                                                          u64 *__restrict__ cand_cnt, prf_imemo *__restrict__ memo,
-                                                          u32 *__restrict__ eps, u64 *__restrict__ counters) {
-    const u32 li = blockIdx.x * blockDim.x + threadIdx.x;
-    if (li >= n_lanes) return;
+// One lane: the walk of (sequence, k) restricted to the landings in [ln.lo, ln.hi).  lane_end[li] = 1 if the walk ended in one
+// of this lane's episodes (at the end of the sequence).  first_end (may be NULL): per (sequence, k) the smallest chunk whose lane
+// ended; a lane behind that chunk is dropped by the host and stops when it sees so (polled every 64 positions).
+// SKIP_ABSORBED: a run whose phase set holds all k phases (k <= max_int) absorbs every mismatch, so it only ends with the sequence:
+// the lane moves to n - k at once, counting the moves it did not make (the memo records of that stretch are not written, so the
+// lookup and hit counters differ from a walk that makes them; the one-lane engine keeps making them).
+template <bool SKIP_ABSORBED>
+__device__ __forceinline__ void walk_lane(const uint8_t *__restrict__ buf, const prf_ilane *__restrict__ lanes, u32 li,
+                                          const u64 *__restrict__ first_last, u32 min_repeats, u32 min_span, u32 max_int, u32 stride,
+                                          prf_icand *__restrict__ cands, u64 *__restrict__ cand_cnt, u32 *__restrict__ lane_end,
+                                          u32 *__restrict__ first_end, prf_imemo *__restrict__ memo, u32 *__restrict__ eps,
+                                          u64 *__restrict__ counters) {
     const prf_ilane ln = lanes[li];
     const u64 f0 = first_last[2 * ln.seq], f1 = first_last[2 * ln.seq + 1];
     const i64 head = f0 == ~0ull ? 0 : (i64)f0;
@@ -69,6 +77,30 @@ __global__ void __launch_bounds__(64) prf_int_walk_kernel(const uint8_t *__restr
     u64 n_cand = 0, steps = 0, lookups = 0, hits = 0, n_ep = 0;
     bool rec_ep = false;  // the current episode has an outcome word
     word_cache ca{-1, 0}, cb{-1, 0};
+    const i64 hi = (i64)ln.hi;
+    const u64 full_mask = k >= 64 ? ~0ull : (1ull << k) - 1ull;
+    u32 *__restrict__ my_end = (first_end && ln.chunk > 0) ? first_end + ln.kslot : nullptr;
+    u32 ended = 0;
+
+    if (ln.lo > 0) {  // the first boundary >= lo: q + 1 with match(q - 1) and not match(q), 1 <= lo - 1 <= q < n - k
+        i64 q = (i64)ln.lo - 1;
+        bool found = false;
+        bool prev = q < n - k && cbyte(base, head + q - 1, ca) == cbyte(base, head + q - 1 + k, cb);
+        for (; q < n - k && q + 1 < hi; q++) {
+            const bool m = cbyte(base, head + q, ca) == cbyte(base, head + q + k, cb);
+            if (prev && !m) {
+                found = true;
+                break;
+            }
+            prev = m;
+        }
+        if (!found) {  // no landing in [lo, hi): nothing to walk
+            cand_cnt[li] = 0;
+            lane_end[li] = 0;
+            return;
+        }
+        pos = q + 1;
+    }
 
     auto open_ep = [&]() {
         rec_ep = use_memo && n_ep < ln.ep_cap;
@@ -100,7 +132,11 @@ __global__ void __launch_bounds__(64) prf_int_walk_kernel(const uint8_t *__restr
                             else n_cand++;  // an overflowing attempt only counts
                         }
                         close_ep(out);
-                        if (out & OUT_END) break;
+                        if (out & OUT_END) {
+                            ended = 1;
+                            break;
+                        }
+                        if (first + 1 >= hi) break;  // the next lane's first landing
                         pos = first + 1;
                         first = -1;
                         run = 0;
@@ -113,7 +149,14 @@ __global__ void __launch_bounds__(64) prf_int_walk_kernel(const uint8_t *__restr
             }
             if (rec_ep) *rec = prf_imemo{(u64)pos, mask, (u64)run, n_ep - 1};
         }
+        if (my_end && ((u64)pos & 63u) == 0 && __atomic_load_n(my_end, __ATOMIC_RELAXED) < ln.chunk) break;  // dropped anyway
 
+        if (SKIP_ABSORBED && run > 0 && mask == full_mask && pos < n - k) {
+            const i64 d = n - k - pos;
+            steps += (u64)d;
+            run += d;
+            pos += d;
+        }
         const bool at_end = pos >= n - k;  // advance() returns False
         if (!at_end) {
             steps++;
@@ -141,6 +184,7 @@ __global__ void __launch_bounds__(64) prf_int_walk_kernel(const uint8_t *__restr
         if (run + k < span || run + k < r_span) {  // returns without reset_traversal(): first interruption and phase set stay
             if (at_end) {
                 close_ep(OUT_END | OUT_NONE);
+                ended = 1;
                 break;
             }
             run = 0;
@@ -172,8 +216,12 @@ __global__ void __launch_bounds__(64) prf_int_walk_kernel(const uint8_t *__restr
             }
         }
         close_ep(out | (at_end ? OUT_END : 0u));
-        if (at_end) break;
+        if (at_end) {
+            ended = 1;
+            break;
+        }
         if (first >= 0) pos = first;  // reset_traversal()
+        if (pos + 1 >= hi) break;     // the next lane's first landing
         first = -1;
         run = 0;
         mask = 0;
@@ -182,10 +230,54 @@ __global__ void __launch_bounds__(64) prf_int_walk_kernel(const uint8_t *__restr
         open_ep();
     }
     cand_cnt[li] = n_cand;
+    lane_end[li] = ended;
+    if (ended && first_end) atomicMin(first_end + ln.kslot, ln.chunk);
     atomicAdd(counters + 0, steps);
     atomicAdd(counters + 1, lookups);
     atomicAdd(counters + 2, hits);
     atomicAdd(counters + 3, n_ep);
+}
+
+__global__ void __launch_bounds__(64) prf_int_walk_kernel(const uint8_t *__restrict__ buf, const prf_ilane *__restrict__ lanes,
+                                                          u32 n_lanes, const u64 *__restrict__ first_last, u32 min_repeats,
+                                                          u32 min_span, u32 max_int, u32 stride, prf_icand *__restrict__ cands,
+                                                          u64 *__restrict__ cand_cnt, u32 *__restrict__ lane_end,
+                                                          prf_imemo *__restrict__ memo, u32 *__restrict__ eps,
+                                                          u64 *__restrict__ counters) {
+    const u32 li = blockIdx.x * blockDim.x + threadIdx.x;
+    if (li >= n_lanes) return;
+    walk_lane<false>(buf, lanes, li, first_last, min_repeats, min_span, max_int, stride, cands, cand_cnt, lane_end, nullptr, memo, eps, counters);
+}
+
+// One lane per wave (the first thread of each 64-thread workgroup): a lane is a chain of dependent loads, and lanes that share a
+// wave pay for each other's branches (every trip round the loop then waits for some lane's memo record).  The gain is in the
+// number of waves in flight, so the other 63 threads stay idle.
+__global__ void __launch_bounds__(64) prf_int_walk_chunk_kernel(const uint8_t *__restrict__ buf, const prf_ilane *__restrict__ lanes,
+                                                                u32 n_lanes, const u64 *__restrict__ first_last, u32 min_repeats,
+                                                                u32 min_span, u32 max_int, u32 stride, prf_icand *__restrict__ cands,
+                                                                u64 *__restrict__ cand_cnt, u32 *__restrict__ lane_end,
+                                                                u32 *__restrict__ first_end, prf_imemo *__restrict__ memo,
+                                                                u32 *__restrict__ eps, u64 *__restrict__ counters) {
+    const u32 li = blockIdx.x;
+    if (li >= n_lanes || threadIdx.x != 0) return;
+    walk_lane<true>(buf, lanes, li, first_last, min_repeats, min_span, max_int, stride, cands, cand_cnt, lane_end, first_end, memo, eps, counters);
+}
+
+// boundaries of each lane's chunk (an upper bound of its episodes, hence of its candidates): one workgroup per lane
+__global__ void __launch_bounds__(256) prf_int_bound_kernel(const uint8_t *__restrict__ buf, const prf_ilane *__restrict__ lanes,
+                                                            const u64 *__restrict__ first_last, u64 *__restrict__ bcount) {
+    const u32 li = blockIdx.x;
+    const prf_ilane ln = lanes[li];
+    const u64 f0 = first_last[2 * ln.seq], f1 = first_last[2 * ln.seq + 1];
+    if (f0 == ~0ull) return;
+    const i64 n = (i64)(f1 - f0), k = ln.k;
+    const uint8_t *__restrict__ s = buf + ln.seq_base + f0;
+    const i64 q0 = ln.lo > 1 ? (i64)ln.lo - 1 : 1;                                  // q + 1 in [lo, hi), 1 <= q < n - k
+    const i64 q1 = (i64)ln.hi - 1 < n - k ? (i64)ln.hi - 1 : n - k;
+    u64 cnt = 0;
+    for (i64 q = q0 + threadIdx.x; q < q1; q += blockDim.x) cnt += (s[q - 1] == s[q - 1 + k]) && (s[q] != s[q + k]);
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(bcount + li, cnt);
 }
 
 __device__ __forceinline__ u64 key_hash(u64 a, u64 b) {
@@ -193,7 +285,11 @@ __device__ __forceinline__ u64 key_hash(u64 a, u64 b) {
     return h ^ (h >> 31);
 }
 
+// lanes of sequence s: lane0[s] + j * n_chunks[s] + c for motif size j and chunk c; the chunks behind the first lane that ended
+// hold landings the walk never reaches and are dropped
 __global__ void __launch_bounds__(64) prf_int_emit_kernel(const prf_ilane *__restrict__ lanes, u32 nk, u32 n_seq,
+                                                          const u32 *__restrict__ lane0, const u32 *__restrict__ n_chunks,
+                                                          const u32 *__restrict__ lane_end,
                                                           const prf_icand *__restrict__ cands, const u64 *__restrict__ cand_cnt,
                                                           const u64 *__restrict__ first_last, const u64 *__restrict__ hash_off,
                                                           const u64 *__restrict__ hash_size, u64 *__restrict__ keys,
@@ -203,14 +299,18 @@ __global__ void __launch_bounds__(64) prf_int_emit_kernel(const prf_ilane *__res
     const u64 head = first_last[2 * s] == ~0ull ? 0 : first_last[2 * s];
     u64 *__restrict__ tab = keys + 2 * hash_off[s];
     const u64 hmask = hash_size[s] - 1;  // a power of two, at least twice the candidates of the sequence
+    const u32 nc = n_chunks[s];
     for (u32 j = 0; j < nk; j++) {
-        const u32 li = s * nk + j;
-        const prf_ilane ln = lanes[li];
-        const u64 cnt = cand_cnt[li];
-        const i64 k = ln.k;
         bool have_prev = false, have_last = false;
         u64 prev_end = 0;
         prf_icand last{};
+        bool ended = false;
+        for (u32 ch = 0; ch < nc && !ended; ch++) {
+        const u32 li = lane0[s] + j * nc + ch;
+        const prf_ilane ln = lanes[li];
+        const u64 cnt = cand_cnt[li];
+        const i64 k = ln.k;
+        ended = lane_end[li] != 0;
         for (u64 i = 0; i < cnt; i++) {
             const prf_icand c = cands[ln.cand_off + i];
             // a candidate equal to the one before it can never change the result
@@ -237,6 +337,7 @@ __global__ void __launch_bounds__(64) prf_int_emit_kernel(const prf_ilane *__res
             rows[at] = prf_ihit_dev{c.start + head, c.end + head, (u32)k, s, c.mask};
             prev_end = c.end;
             have_prev = true;
+        }
         }
     }
 }
@@ -300,20 +401,31 @@ hipError_t prf_launch_int_trim(hipStream_t st, const uint8_t *buf, const u64 *se
 }
 
 hipError_t prf_launch_int_walk(hipStream_t st, const uint8_t *buf, const prf_ilane *lanes, u32 n_lanes, const u64 *first_last,
-                               u32 min_repeats, u32 min_span, u32 max_int, u32 stride, prf_icand *cands, u64 *cand_cnt,
-                               prf_imemo *memo, u32 *eps, u64 *counters) {
+                               u32 min_repeats, u32 min_span, u32 max_int, u32 stride, prf_icand *cands, u64 *cand_cnt, u32 *lane_end,
+                               u32 *first_end, prf_imemo *memo, u32 *eps, u64 *counters) {
     if (!n_lanes) return hipSuccess;
-    hipLaunchKernelGGL(prf_int_walk_kernel, dim3((n_lanes + 63) / 64), dim3(64), 0, st, buf, lanes, n_lanes, first_last, min_repeats,
-                       min_span, max_int, stride, cands, cand_cnt, memo, eps, counters);
+    if (first_end)
+        hipLaunchKernelGGL(prf_int_walk_chunk_kernel, dim3(n_lanes), dim3(64), 0, st, buf, lanes, n_lanes, first_last, min_repeats,
+                           min_span, max_int, stride, cands, cand_cnt, lane_end, first_end, memo, eps, counters);
+    else
+        hipLaunchKernelGGL(prf_int_walk_kernel, dim3((n_lanes + 63) / 64), dim3(64), 0, st, buf, lanes, n_lanes, first_last, min_repeats,
+                           min_span, max_int, stride, cands, cand_cnt, lane_end, memo, eps, counters);
     return hipGetLastError();
 }
 
-hipError_t prf_launch_int_emit(hipStream_t st, const prf_ilane *lanes, u32 nk, u32 n_seq, const prf_icand *cands, const u64 *cand_cnt,
-                               const u64 *first_last, const u64 *hash_off, const u64 *hash_size, u64 *keys, prf_ihit_dev *rows,
+hipError_t prf_launch_int_bound(hipStream_t st, const uint8_t *buf, const prf_ilane *lanes, u32 n_lanes, const u64 *first_last,
+                                u64 *bcount) {
+    if (!n_lanes) return hipSuccess;
+    hipLaunchKernelGGL(prf_int_bound_kernel, dim3(n_lanes), dim3(256), 0, st, buf, lanes, first_last, bcount);
+    return hipGetLastError();
+}
+
+hipError_t prf_launch_int_emit(hipStream_t st, const prf_ilane *lanes, u32 nk, u32 n_seq, const u32 *lane0, const u32 *n_chunks,
+                               const u32 *lane_end, const prf_icand *cands, const u64 *cand_cnt, const u64 *first_last, const u64 *hash_off, const u64 *hash_size, u64 *keys, prf_ihit_dev *rows,
                                u64 *row_cnt) {
     if (!n_seq) return hipSuccess;
-    hipLaunchKernelGGL(prf_int_emit_kernel, dim3((n_seq + 63) / 64), dim3(64), 0, st, lanes, nk, n_seq, cands, cand_cnt, first_last,
-                       hash_off, hash_size, keys, rows, row_cnt);
+    hipLaunchKernelGGL(prf_int_emit_kernel, dim3((n_seq + 63) / 64), dim3(64), 0, st, lanes, nk, n_seq, lane0, n_chunks, lane_end, cands, cand_cnt,
+                       first_last, hash_off, hash_size, keys, rows, row_cnt);
     return hipGetLastError();
 }
 

@@ -110,11 +110,13 @@ def _masked_motif(seq, start, k, nmask):
 
 def _interrupted_rows(seqs, fs, context=None):
     """Interrupted repeats of whole sequences, all in one call (csrc/scan_interrupted.hip): numpy rows (start, end, k, contig,
-    nmask) sorted by (contig, start, end)."""
+    nmask) sorted by (contig, start, end).  The walk runs in chunks of fs.interrupted_chunk landing positions (default: the
+    library's PRF_INT_CHUNK; 0: one lane per motif size); the rows do not depend on it."""
     ctx = context or prf_native.default_context()
+    chunk = getattr(fs, "interrupted_chunk", None)
     try:
         rows, _stats = ctx.scan_interrupted(seqs, fs.min_motif_size, fs.max_motif_size, fs.min_repeats, fs.min_span,
-                                            fs.max_interruptions)
+                                            fs.max_interruptions, chunk=prf_native.INT_CHUNK if chunk is None else chunk)
     except prf_native.PrfError as exc:
         if exc.code in (prf_native.PRF_EINVAL, prf_native.PRF_ESYMBOL, prf_native.PRF_EUNSUPPORTED):
             raise ValueError(exc.message) from None
@@ -200,6 +202,9 @@ def _build_parser():
     g.add_argument("--max-interruptions", type=int, default=0,
                    help="(the reference's RepeatTracker) how many positions within the motif may vary across repeats; 0: perfect "
                         "repeats only.  Whole sequences only (no --interval), min repeats >= 2, max motif size <= 64.")
+    g.add_argument("--interrupted-chunk", type=int, default=None, metavar="N",
+                   help="With --max-interruptions > 0: positions of a sequence that one GPU lane walks (default: the library's, "
+                        "2^20; 0: one lane per motif size).  The output does not depend on it.")
     p.add_argument("-i", "--interval", help="Restrict the scan to chrom:start_0based-end.")
     p.add_argument("-p", "--plot", help="Accepted for compatibility; plotting is not part of this build.")
     p.add_argument("-o", "--output-prefix", help="Prefix of the output TSV (and BED, for FASTA input).")
@@ -489,6 +494,8 @@ def main(argv=None):
         parser.error(f"--min-span is set to {args.min_span}. It must be at least 1.")
     if args.max_interruptions < 0:
         parser.error(f"--max-interruptions is set to {args.max_interruptions}. It must be at least 0.")
+    if args.interrupted_chunk is not None and (args.interrupted_chunk < 0 or 0 < args.interrupted_chunk < prf_native.INT_CHUNK_MIN):
+        parser.error(f"--interrupted-chunk is set to {args.interrupted_chunk}. It must be 0 or at least {prf_native.INT_CHUNK_MIN}.")
     if os.path.isfile(args.input_sequence):
         _scan_fasta(args, parser)
     elif set(args.input_sequence.upper()) <= set("ACGTN"):

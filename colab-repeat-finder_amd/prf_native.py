@@ -62,6 +62,8 @@ class _IHits(ctypes.Structure):
 IHIT_DTYPE = [("start", "<u8"), ("end", "<u8"), ("k", "<u4"), ("contig", "<u4"), ("nmask", "<u8")]
 MEMO_STRIDE = 8
 MEMO_SLOTS = 1 << 22
+INT_CHUNK = 1 << 20    # PRF_INT_CHUNK: landing positions per lane of the chunked interrupted walk
+INT_CHUNK_MIN = 2      # PRF_INT_CHUNK_MIN
 
 
 class ScanStats(ctypes.Structure):
@@ -80,7 +82,8 @@ EXPORTS = ["prf_abi_version", "prf_device_count", "prf_last_error", "prf_open", 
            "prf_fasta_entry", "prf_fasta_close", "prf_write_bed", "prf_write_tsv", "prf_genome_synth", "prf_scan_timings", "prf_set_row_sink", "prf_fasta_open_contig", "prf_scan_genome_async",
            "prf_scan_wait", "prf_genome_standin", "prf_genome_select", "prf_genome_tile_classes", "prf_tile_positions", "prf_scan_timings_split", "prf_last_hits_packed_to_device",
            "prf_genome_contig_bases", "prf_scan_literal", "prf_scan_genome_async_packed", "prf_stream_wait_for",
-           "prf_genome_footprint", "prf_scan_interrupted", "prf_scan_interrupted_ex", "prf_free_ihits"]
+           "prf_genome_footprint", "prf_scan_interrupted", "prf_scan_interrupted_ex", "prf_free_ihits",
+           "prf_scan_interrupted_chunked"]
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -152,6 +155,8 @@ def load_library():
             ctypes.POINTER(_IHits), ctypes.POINTER(ScanStats)]
         lib.prf_scan_interrupted_ex.argtypes = [vp, ctypes.POINTER(_Contig), ctypes.c_int] + [ctypes.c_uint32] * 6 + [
             ctypes.c_uint64, ctypes.POINTER(_IHits), ctypes.POINTER(ScanStats), ctypes.POINTER(ctypes.c_uint64)]
+        lib.prf_scan_interrupted_chunked.argtypes = [vp, ctypes.POINTER(_Contig), ctypes.c_int] + [ctypes.c_uint32] * 6 + [
+            ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(_IHits), ctypes.POINTER(ScanStats), ctypes.POINTER(ctypes.c_uint64)]
         lib.prf_free_ihits.argtypes = [ctypes.POINTER(_IHits)]
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
@@ -354,19 +359,28 @@ class Context:
             self.lib.prf_free_hits(ctypes.byref(hits))
 
     def scan_interrupted(self, seqs, kmin, kmax, min_repeats, min_span, max_interruptions, memo_stride=None, memo_slots=None,
-                         counters=False):
+                         counters=False, chunk=None):
         """Interrupted repeats of many whole sequences in one call (prf_scan_interrupted): (rows, stats[, counters]).  rows: numpy
         records (start, end, k, contig, nmask) sorted by (contig, start, end); bit i of nmask = phase i of the motif may vary.
         memo_stride / memo_slots: the walk's memo table (the rows do not depend on it); counters: also return a dict of the
-        walk's steps, memo lookups, memo hits and recorded episodes."""
+        walk's steps, memo lookups, memo hits and recorded episodes.  chunk: None = one lane per (sequence, motif size)
+        (prf_scan_interrupted_ex); an integer = prf_scan_interrupted_chunked with that many landing positions per lane (0: one
+        lane again; INT_CHUNK: the library's default), and the counters then also hold `lanes` and `dropped_lanes`.  The rows
+        do not depend on it."""
         import numpy as np
         arr, _keep = _contig_array(list(seqs))
         hits, stats = _IHits(), ScanStats()
-        ctr = (ctypes.c_uint64 * 4)()
-        _check(self.lib, self.lib.prf_scan_interrupted_ex(
-            self._h, arr, len(seqs), kmin, kmax, min_repeats, min_span, max_interruptions,
-            MEMO_STRIDE if memo_stride is None else memo_stride, MEMO_SLOTS if memo_slots is None else memo_slots,
-            ctypes.byref(hits), ctypes.byref(stats), ctr))
+        ctr = (ctypes.c_uint64 * 6)()
+        stride = MEMO_STRIDE if memo_stride is None else memo_stride
+        slots = MEMO_SLOTS if memo_slots is None else memo_slots
+        if chunk is None:
+            _check(self.lib, self.lib.prf_scan_interrupted_ex(
+                self._h, arr, len(seqs), kmin, kmax, min_repeats, min_span, max_interruptions, stride, slots,
+                ctypes.byref(hits), ctypes.byref(stats), ctr))
+        else:
+            _check(self.lib, self.lib.prf_scan_interrupted_chunked(
+                self._h, arr, len(seqs), kmin, kmax, min_repeats, min_span, max_interruptions, stride, slots, chunk,
+                ctypes.byref(hits), ctypes.byref(stats), ctr))
         try:
             n = hits.n
             if n == 0:
@@ -377,7 +391,10 @@ class Context:
         finally:
             self.lib.prf_free_ihits(ctypes.byref(hits))
         if counters:
-            return rows, stats, {"steps": ctr[0], "lookups": ctr[1], "hits": ctr[2], "episodes": ctr[3]}
+            out = {"steps": ctr[0], "lookups": ctr[1], "hits": ctr[2], "episodes": ctr[3]}
+            if chunk is not None:
+                out.update(lanes=ctr[4], dropped_lanes=ctr[5])
+            return rows, stats, out
         return rows, stats
 
     def scan_literal(self, seq, kmin, kmax, min_repeats, min_span, stop=None):

@@ -193,7 +193,7 @@ typedef struct prf_ihits {
 } prf_ihits;
 
 #define PRF_MEMO_STRIDE 8u          /* prf_scan_interrupted: a state is recorded every 8 positions ...          */
-#define PRF_MEMO_SLOTS (1ull << 22) /* ... in a table of at most this many records per (contig, motif size)     */
+#define PRF_MEMO_SLOTS (1ull << 22) /* ... in a table of at most this many records per lane                     */
 
 int prf_scan_interrupted(prf_ctx *ctx, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax,
                          uint32_t min_repeats, uint32_t min_span, uint32_t max_interruptions, prf_ihits *out,
@@ -204,6 +204,18 @@ int prf_scan_interrupted(prf_ctx *ctx, const prf_contig *contigs, int n_contigs,
 int prf_scan_interrupted_ex(prf_ctx *ctx, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax,
                             uint32_t min_repeats, uint32_t min_span, uint32_t max_interruptions, uint32_t memo_stride,
                             uint64_t memo_slots, prf_ihits *out, prf_scan_stats *stats, uint64_t *counters);
+/* The walk of each (contig, motif size) cut into chunks of `chunk` landing positions, one GPU wave per chunk (every
+ * jump back lands in the clean state on the next position behind a match followed by a mismatch, so the episodes that start in
+ * different chunks do not depend on each other).  The rows do not depend on `chunk`.  chunk == 0: one lane per (contig, motif
+ * size), the engine of prf_scan_interrupted_ex; 0 < chunk < PRF_INT_CHUNK_MIN: PRF_EINVAL (a lane looks for its first landing
+ * from position chunk - 2 on).  counters (may be NULL) receives six words: the four of prf_scan_interrupted_ex, the lanes
+ * launched, and the lanes dropped because a lane of an earlier chunk of their (contig, motif size) reached the end of the
+ * contig.  prf_scan_interrupted() is this call with PRF_MEMO_STRIDE, PRF_MEMO_SLOTS and PRF_INT_CHUNK. */
+#define PRF_INT_CHUNK_MIN 2u
+#define PRF_INT_CHUNK (1ull << 20)
+int prf_scan_interrupted_chunked(prf_ctx *ctx, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax,
+                                 uint32_t min_repeats, uint32_t min_span, uint32_t max_interruptions, uint32_t memo_stride,
+                                 uint64_t memo_slots, uint64_t chunk, prf_ihits *out, prf_scan_stats *stats, uint64_t *counters);
 void prf_free_ihits(prf_ihits *hits);
 
 /* Pipelined scans.  prf_scan_genome_async() enqueues a scan and returns its serial number at once;

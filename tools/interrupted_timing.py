@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Interrupted repeats (prf_scan_interrupted) on a chromosome-sized stand-in: one JSON line with the device time, the walk's
-steps per position and the memo hit rate.
+"""Interrupted repeats (prf_scan_interrupted_chunked) on a chromosome-sized stand-in: one JSON line with the device time (walk and
+emission + sort apart), the lanes launched and dropped, the walk's steps per position and the memo hit rate.
 
     python3 tools/interrupted_timing.py [--length 50818468] [--kmin 1 --kmax 6 --min-repeats 3 --min-span 9 --max-interruptions 1]
+    python3 tools/interrupted_timing.py --chunk 262144              # landing positions per lane (default: the library's; 0: one
+                                                                    # lane per motif size, the engine before chunks)
     python3 tools/interrupted_timing.py --model [--length ...]      # the CPU model (tests/interrupted_model.py) instead, no GPU
 """
 import argparse
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--max-interruptions", type=int, default=1)
     ap.add_argument("--memo-stride", type=int, default=8)
     ap.add_argument("--memo-slots", type=int, default=1 << 22)
+    ap.add_argument("--chunk", type=int, default=None, help="landing positions per GPU lane (default: PRF_INT_CHUNK; 0: one lane per k)")
     ap.add_argument("--repeat", type=int, default=2, help="GPU: calls (the first one warms up)")
     ap.add_argument("--model", action="store_true", help="time the CPU model instead of the GPU")
     args = ap.parse_args()
@@ -44,13 +47,15 @@ def main():
         res.update(engine="cpu_model", seconds=round(time.perf_counter() - t, 2), rows=len(rows))
     else:
         import prf_native
+        chunk = prf_native.INT_CHUNK if args.chunk is None else args.chunk
         ctx = prf_native.Context(0)
         for _ in range(args.repeat):
             t = time.perf_counter()
-            rows, stats, ctr = ctx.scan_interrupted([seq], *p, memo_stride=args.memo_stride, memo_slots=args.memo_slots, counters=True)
+            rows, stats, ctr = ctx.scan_interrupted([seq], *p, memo_stride=args.memo_stride, memo_slots=args.memo_slots, counters=True,
+                                                    chunk=chunk)
             wall = time.perf_counter() - t
         ctx.close()
-        res.update(engine="gpu", rows=len(rows), wall_s=round(wall, 3), scan_ms=round(stats.scan_ms, 2), walk_ms=round(stats.phase1_ms, 2),
+        res.update(engine="gpu", chunk=chunk, lanes=int(ctr["lanes"]), dropped_lanes=int(ctr["dropped_lanes"]), rows=len(rows), wall_s=round(wall, 3), scan_ms=round(stats.scan_ms, 2), walk_ms=round(stats.phase1_ms, 2),
                    emit_sort_ms=round(stats.phase2_ms, 2), candidates=int(stats.n_candidates), launches=int(stats.n_launches),
                    episodes_recorded=int(ctr["episodes"]))
     body = args.length - n_head - min(10_000, args.length // 100)
