@@ -1,6 +1,9 @@
-// api.cpp -- the C ABI of libprf (include/prf.h): contexts, genome residency, scan orchestration.
+// api.cpp -- the C ABI of libprf (include/prf.h) but for the FASTA / BED entry points (fasta_io.cpp) and the interrupted
+// repeats (interrupted.cpp): contexts and the error text, genome residency, the perfect scan with its passes (fused_pass,
+// exotic_pass, generic_pass under run_passes), the literal lane (min_repeats == 1: literal_device and its callers), pipelined
+// scans, row hand-off to the device.  What it shares with interrupted.cpp is in prf_ctx.h.
 //
-// Host-side shape of one scan (what replaces the body of the reference's detect_repeats(),
+// Host-side shape of one perfect scan (what replaces the body of the reference's detect_repeats(),
 // perfect_repeat_finder.py:33-81):
 //   fused path (kmax <= 480): two launches -- the scan kernel (persistent workgroups: scan + verify + the rows of every
 //   tile sorted into its slab) and the row gather (slabs -> ONE array sorted by (contig, start, end), as the reference
@@ -16,60 +19,24 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <string>
 #include <vector>
 
-#include "../../include/prf.h"
-#include "prf_host.h"
+#include "prf_ctx.h"
 #include "scan_vertical.h"
 
 static thread_local std::string g_err;
 
 static const u64 PRF_FRONT_PAD = 8;  // readable words in front of every linear plane (X = all ones there)
 
-static int vfail(int code, const char *fmt, va_list ap) {
+int prf_set_error(int code, const char *fmt, ...) {
     char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
     vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
     g_err = buf;
     return code;
-}
-
-static int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vfail(code, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// for the other host-side translation units of the library
-int prf_set_error(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vfail(code, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIPCHK(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess)                                                                                 \
-            return fail(e_ == hipErrorOutOfMemory ? PRF_ENOMEM : PRF_EHIP, "%s failed: %s (%s:%d)", #expr,    \
-                        hipGetErrorString(e_), __FILE__, __LINE__);                                           \
-    } while (0)
-
-// The C boundary: no exception leaves the library
-template <class F>
-static int guarded(const char *name, F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        return fail(PRF_ENOMEM, "%s: out of host memory", name);
-    } catch (...) {
-        return fail(PRF_EHIP, "%s: unexpected exception", name);
-    }
 }
 
 // A device array of at least `want` elements; a smaller one is replaced (its contents are not kept)
@@ -83,61 +50,6 @@ static int grow(T *&p, u64 &cap, u64 want) {
     cap = want;
     return PRF_OK;
 }
-
-struct prf_ctx {
-    int dev = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    // fused path: one event pair per scan, in a ring, so that the kernel times of the last PRF_TIMING_RING scans can
-    // be read after a timing loop (prf_scan_timings) instead of waiting for the events inside every scan
-    hipEvent_t ring[3 * PRF_TIMING_RING] = {};  // per scan: before the scan kernel, between the two kernels, after the gather
-    u64 *d_counters = nullptr;   // generic path + packer
-    u64 *h_counters = nullptr;   // pinned, device-mapped: the fused path's last kernel writes the counters here
-    u64 *h_counters_dev = nullptr;  // device address of h_counters
-    u64 *d_vcounters = nullptr;  // fused path: two counter blocks used alternately (the idle one is cleared on the device)
-    u64 *d_side_cnt = nullptr;   // pipelined wire hand-off: long rows packed so far (zero between packs)
-    void *lit_scratch = nullptr;  // the literal lane's sort scratch (scan_literal.hip::prf_lit_sort_unique): kept between calls
-    size_t lit_scratch_bytes = 0;
-    hipEvent_t ev_handoff = nullptr;  // prf_stream_wait_for
-    u32 parity = 0;
-    u64 scan_seq = 0;
-    // generic path scratch
-    u64 *d_cand = nullptr;
-    u64 cand_cap = 0;
-    prf_hit_dev *d_hits = nullptr;  // flat rows: generic path output, or the compacted rows of the fused path
-    u64 hit_cap = 0;
-    prf_hit_dev *sink = nullptr;    // caller-owned device array the rows go to instead (prf_set_row_sink)
-    u64 sink_cap = 0;
-    struct last_scan {              // where the rows of the last scan are
-        const prf_hit_dev *rows = nullptr;
-        u64 nhits = 0;
-        u32 kmax = 0;               // its largest motif size (the 8-byte wire rows hold 9 bits)
-    } last;
-    // pipelined scans (prf_scan_genome_async / prf_scan_wait): two slots used alternately, each with its own host
-    // counter block and row array; slot 0 shares them with the synchronous path
-    struct async_slot {
-        u64 seq = 0;            // scan in this slot (0: free)
-        u64 *h = nullptr;       // mapped host counter block (+ serial number word)
-        u64 *h_dev = nullptr;
-        prf_hit_dev *rows = nullptr;
-        u64 positions = 0;
-        u32 tiles = 0;
-        u32 kmax = 0;
-    } slot[2];
-    u64 async_n = 0;
-    u64 *h_async = nullptr;         // slot 1's counter block
-    prf_hit_dev *d_hits_async = nullptr;
-    u64 hit_cap_async = 0;
-    // fused (bit-sliced) path scratch: one row slab and one row count per launch slot (= scanned tile)
-    u64 *d_slabs = nullptr;         // 8-byte rows (scan_vertical.h)
-    u64 *d_long_ends = nullptr;     // per launch slot: true ends of the rows whose span is clipped in the 8-byte form
-    u32 *d_slab_count = nullptr;
-    u32 *d_block_sum = nullptr;     // rows per PRF_GATHER_SLOTS launch slots; zero between scans (the gather clears it)
-    u64 slab_slots = 0;
-    u32 slab_cap = 0;
-    u64 *stamps_buf = nullptr;      // diagnostic (PRF_STAMPS) builds only
-    u32 stamps_n = 0;
-};
 
 struct prf_genome {
     prf_ctx *ctx = nullptr;
@@ -578,20 +490,6 @@ static int launch_fused(prf_ctx *c, const prf_genome *g, const prf_vplan &plan, 
 static int literal_genome(prf_ctx *c, const prf_genome *g, u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_hits *out,
                           prf_scan_stats *stats);
 
-// Same conditions, same wording as the reference's ValueErrors (perfect_repeat_finder.py:23-30), then the library's limits:
-// the motif sizes a resident genome was packed for (kmax_hint), or the literal lane's 60000 (kmax_hint 0).
-static int check_params(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, u32 kmax_hint) {
-    if (kmin < 1) return fail(PRF_EINVAL, "min_motif_size is set to %u. It must be at least 1.", kmin);
-    if (kmax < kmin) return fail(PRF_EINVAL, "max_motif_size is set to %u. It must be at least min_motif_size.", kmax);
-    if (min_repeats < 1) return fail(PRF_EINVAL, "min_repeats is set to %u. It must be at least 1.", min_repeats);
-    if (min_span < 1) return fail(PRF_EINVAL, "min_span is set to %u. It must be at least 1.", min_span);
-    if (min_repeats > 1000000u || min_span > (1u << 30)) return fail(PRF_EINVAL, "threshold out of range");
-    if (kmax_hint && kmax > kmax_hint)
-        return fail(PRF_EUNSUPPORTED, "max_motif_size %u exceeds the kmax_hint %u this genome was packed with", kmax, kmax_hint);
-    if (kmax > 60000) return fail(PRF_EUNSUPPORTED, "max_motif_size %u > 60000", kmax);
-    return PRF_OK;
-}
-
 struct scan_params {
     u32 kmin, kmax, min_repeats, min_span;
 };
@@ -906,29 +804,22 @@ int prf_scan_genome(prf_ctx *c, const prf_genome *g, uint32_t kmin, uint32_t kma
 // evaluates the reference's flush call as written; the rows are then sorted like reference :81 and reduced to the shortest
 // motif per (start, end) -- what the reference's dictionary holds at the end (utils/perfect_repeat_tracker.py:93-101) -- on the
 // device as well (prf_lit_sort_unique).
-namespace {
-struct dev_free {
-    void *p = nullptr;
-    ~dev_free() { if (p) (void)hipFree(p); }
-};
-}  // namespace
-
 // d_seq: L bytes on the device (16-byte aligned: the 64-positions kernel reads whole 16-byte groups, 16 readable bytes behind them); upper: not upper-cased / validated yet
 // front: the N trimmed off the front of the contig -- the rows and the position of an unsupported symbol are shifted by it
 static int literal_device(prf_ctx *c, uint8_t *d_seq, u64 L, bool upper, u32 contig_index, u32 kmin, u32 kmax, u32 min_repeats,
                           u32 min_span, u64 stop, std::vector<prf_hit> &rows_out, float *ms, u32 *launches, u64 front) {
     if (stop > L) stop = L;
-    dev_free rows;
+    dev_array<prf_hit_dev> rows;
     u64 cap = L / 16 + 4096;
     u64 *h = c->h_counters;
     for (int attempt = 0;; attempt++) {
-        HIPCHK(hipMalloc(&rows.p, cap * sizeof(prf_hit_dev)));
+        if (const int rc = rows.alloc(cap)) return rc;
         HIPCHK(hipMemsetAsync(c->d_counters, 0, PRF_CNT_N * sizeof(u64), c->stream));
         HIPCHK(hipMemsetAsync(c->d_counters + PRF_CNT_BADPOS, 0xFF, sizeof(u64), c->stream));
         HIPCHK(hipEventRecord(c->ev[0], c->stream));
         if (attempt == 0 && upper) HIPCHK(prf_launch_lit_upper(c->stream, d_seq, L, c->d_counters + PRF_CNT_BADPOS));
-        HIPCHK(prf_launch_lit_events(c->stream, d_seq, L, kmin, kmax, min_repeats, min_span, stop, contig_index,
-                                     (prf_hit_dev *)rows.p, cap, c->d_counters));
+        HIPCHK(prf_launch_lit_events(c->stream, d_seq, L, kmin, kmax, min_repeats, min_span, stop, contig_index, rows.p, cap,
+                                     c->d_counters));
         HIPCHK(hipEventRecord(c->ev[1], c->stream));
         HIPCHK(hipMemcpyAsync(h, c->d_counters, PRF_CNT_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -947,11 +838,10 @@ static int literal_device(prf_ctx *c, uint8_t *d_seq, u64 L, bool upper, u32 con
         if (n <= cap) {
             // sorted by (start, end) and reduced to the shortest motif per (start, end) on the device (scan_literal.hip)
             if (n) {
-                dev_free uniq;
-                HIPCHK(hipMalloc(&uniq.p, n * sizeof(prf_hit_dev)));
+                dev_array<prf_hit_dev> uniq;
+                if (const int rc = uniq.alloc(n)) return rc;
                 u64 *d_n = c->d_counters + PRF_CNT_HITS;  // read above; reused for the number of rows that stay
-                HIPCHK(prf_lit_sort_unique(c->stream, (const prf_hit_dev *)rows.p, n, (prf_hit_dev *)uniq.p, d_n, &c->lit_scratch,
-                                           &c->lit_scratch_bytes));
+                HIPCHK(prf_lit_sort_unique(c->stream, rows.p, n, uniq.p, d_n, &c->lit_scratch, &c->lit_scratch_bytes));
                 HIPCHK(hipMemcpyAsync(h, d_n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
                 HIPCHK(hipStreamSynchronize(c->stream));
                 const u64 kept = h[0];
@@ -972,8 +862,6 @@ static int literal_device(prf_ctx *c, uint8_t *d_seq, u64 L, bool upper, u32 con
             return PRF_OK;
         }
         if (attempt >= 2) return fail(PRF_EHIP, "prf_scan_literal: the row count changed between two runs");
-        (void)hipFree(rows.p);
-        rows.p = nullptr;
         cap = n;
     }
 }
@@ -983,10 +871,10 @@ static int literal_one(prf_ctx *c, const prf_contig &ct, u32 contig_index, u32 k
     const u64 L = ct.len;
     if (L && !ct.ascii) return fail(PRF_EINVAL, "prf_scan_literal: NULL sequence");
     if (L >= (1ull << 40)) return fail(PRF_EUNSUPPORTED, "prf_scan_literal: input too large (2^40 positions)");
-    dev_free seq;
-    HIPCHK(hipMalloc(&seq.p, L + 16));
+    dev_array<uint8_t> seq;
+    if (const int rc = seq.alloc(L + 16)) return rc;
     if (L) HIPCHK(hipMemcpyAsync(seq.p, ct.ascii, L, hipMemcpyHostToDevice, c->stream));
-    return literal_device(c, (uint8_t *)seq.p, L, true, contig_index, kmin, kmax, min_repeats, min_span, stop, rows_out, ms, launches, front);
+    return literal_device(c, seq.p, L, true, contig_index, kmin, kmax, min_repeats, min_span, stop, rows_out, ms, launches, front);
 }
 
 // what the literal lane refuses on a context: a row sink, pipelined scans in flight
@@ -1044,13 +932,13 @@ static int literal_genome(prf_ctx *c, const prf_genome *g, u32 kmin, u32 kmax, u
             if (c->h_counters[0] != ~0ull) { lo = c->h_counters[0]; hi = c->h_counters[1]; }
         }
         const u64 n = hi - lo;
-        dev_free seq;
-        HIPCHK(hipMalloc(&seq.p, n + 16));
+        dev_array<uint8_t> seq;
+        if (const int rc = seq.alloc(n + 16)) return rc;
         if (n) {
-            HIPCHK(prf_launch_lit_unpack(c->stream, g->H, g->L, g->X, g->E, g->base[ci] + lo, n, (uint8_t *)seq.p));
+            HIPCHK(prf_launch_lit_unpack(c->stream, g->H, g->L, g->X, g->E, g->base[ci] + lo, n, seq.p));
             launches++;
         }
-        const int rc = literal_device(c, (uint8_t *)seq.p, n, false, (u32)ci, kmin, kmax, min_repeats, min_span, n, rows, &ms, &launches, lo);
+        const int rc = literal_device(c, seq.p, n, false, (u32)ci, kmin, kmax, min_repeats, min_span, n, rows, &ms, &launches, lo);
         if (rc) return rc;
     }
     return literal_finish(c, rows, ms, launches, g->positions, out, stats);
@@ -1106,327 +994,6 @@ int prf_scan(prf_ctx *c, const prf_contig *contigs, int n_contigs, uint32_t kmin
     rc = prf_scan_genome(c, g, kmin, kmax, min_repeats, min_span, flags, out, stats);
     prf_genome_free(g);
     return rc;
-}
-
-// ---- interrupted repeats (scan_interrupted.hip) ----
-// Whole sequences, one call: upload + upper-case (+ the first byte that is not a letter) + N-trimming on the device, the walk
-// (one lane per (sequence, k); candidate lists grow by running again with the exact counts), then emission + sort.
-namespace {
-struct dev_buf {
-    void *p = nullptr;
-    ~dev_buf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        HIPCHK(hipMalloc(&p, bytes ? bytes : 16));
-        return PRF_OK;
-    }
-};
-}  // namespace
-
-static int interrupted_check(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, u32 max_interruptions, u32 memo_stride) {
-    int rc = check_params(kmin, kmax, min_repeats, min_span, 0);
-    if (rc) return rc;
-    if (max_interruptions < 1)
-        return fail(PRF_EINVAL, "max_interruptions is %u: prf_scan_interrupted serves max_interruptions >= 1 (0 is prf_scan's perfect path)",
-                    max_interruptions);
-    if (min_repeats < 2)
-        return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: min_repeats == 1 is not supported with interruptions (min_repeats >= 2)");
-    if (kmax > 64) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: max_motif_size %u > 64 (the phase set is one 64-bit mask)", kmax);
-    if (memo_stride & (memo_stride - 1u)) return fail(PRF_EINVAL, "prf_scan_interrupted: memo_stride %u is not a power of two", memo_stride);
-    return PRF_OK;
-}
-
-static int interrupted_impl(prf_ctx *c, const prf_contig *contigs, int n_contigs, u32 kmin, u32 kmax, u32 min_repeats, u32 min_span,
-                            u32 max_int, u32 memo_stride, u64 memo_slots, u64 chunk, prf_ihits *out, prf_scan_stats *stats,
-                            uint64_t *counters_out) {
-    // chunk == 0: one lane per (sequence, k), one lane per thread (prf_scan_interrupted_ex).  Otherwise the landings of each
-    // (sequence, k) are cut into chunks of `chunk` positions, one lane per wave, and counters_out has six words.
-    if (out) { out->rows = nullptr; out->n = 0; }
-    int rc = interrupted_check(kmin, kmax, min_repeats, min_span, max_int, memo_stride);
-    if (rc) return rc;
-    if (chunk && chunk < PRF_INT_CHUNK_MIN)
-        return fail(PRF_EINVAL, "prf_scan_interrupted_chunked: chunk %llu is below the minimum of %u positions (0 = one lane per motif size)",
-                    (unsigned long long)chunk, (unsigned)PRF_INT_CHUNK_MIN);
-    if (!c) return fail(PRF_EINVAL, "prf_scan_interrupted: NULL context");
-    if (n_contigs < 0 || (n_contigs && !contigs)) return fail(PRF_EINVAL, "prf_scan_interrupted: bad contig array");
-    for (int i = 0; i < n_contigs; i++) {
-        if (contigs[i].len && !contigs[i].ascii) return fail(PRF_EINVAL, "prf_scan_interrupted: NULL sequence");
-        if (contigs[i].len >= (1ull << 40)) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: input too large (2^40 positions)");
-    }
-    if (c->slot[0].seq || c->slot[1].seq) return fail(PRF_EINVAL, "prf_scan_interrupted: pipelined scans are in flight on this context");
-    HIPCHK(hipSetDevice(c->dev));
-    const u32 nk = kmax - kmin + 1, n_seq = (u32)n_contigs;
-    if ((u64)n_seq * nk > 0x7fffffffull) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: too many (sequence, motif size) lanes");
-
-    // host plan: sequence placement (16-byte aligned, 16 readable bytes behind each), trim chunks
-    std::vector<u64> seq_base(std::max<u32>(1, n_seq)), chunks;
-    u64 total = 0, positions = 0;
-    for (u32 i = 0; i < n_seq; i++) {
-        seq_base[i] = total;
-        total += (contigs[i].len + 16 + 15) & ~15ull;
-        positions += contigs[i].len;
-        for (u64 b = 0; b < contigs[i].len; b += 4096) {
-            chunks.push_back(i);
-            chunks.push_back(b);
-            chunks.push_back(std::min<u64>(contigs[i].len, b + 4096));
-        }
-    }
-    const u32 n_chunks = (u32)(chunks.size() / 3);
-
-    dev_buf d_seq, d_base, d_chunks, d_fl, d_lanes, d_cands, d_cnt, d_end, d_first_end, d_bcount, d_memo, d_eps, d_ctr;
-    if ((rc = d_seq.alloc(total + 16)) || (rc = d_base.alloc(seq_base.size() * 8)) || (rc = d_chunks.alloc(chunks.size() * 8)) ||
-        (rc = d_fl.alloc(2 * 8 * (size_t)std::max<u32>(1, n_seq))) || (rc = d_ctr.alloc(8 * 8)))
-        return rc;
-    hipStream_t st = c->stream;
-    HIPCHK(hipMemsetAsync(d_seq.p, 'N', total + 16, st));  // the gaps are letters: the symbol check passes over them
-    for (u32 i = 0; i < n_seq; i++)
-        if (contigs[i].len) HIPCHK(hipMemcpyAsync((uint8_t *)d_seq.p + seq_base[i], contigs[i].ascii, contigs[i].len, hipMemcpyHostToDevice, st));
-    std::vector<u64> fl(2 * (size_t)std::max<u32>(1, n_seq));
-    for (size_t i = 0; i < fl.size(); i += 2) { fl[i] = ~0ull; fl[i + 1] = 0; }
-    HIPCHK(hipMemcpyAsync(d_base.p, seq_base.data(), seq_base.size() * 8, hipMemcpyHostToDevice, st));
-    if (!chunks.empty()) HIPCHK(hipMemcpyAsync(d_chunks.p, chunks.data(), chunks.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_fl.p, fl.data(), fl.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_ctr.p, 0, 8 * 8, st));
-    HIPCHK(hipMemsetAsync(d_ctr.p, 0xFF, 8, st));  // word 0: first byte that is not a letter
-    u32 launches = 0;
-    HIPCHK(hipEventRecord(c->ev[0], st));
-    if (total) HIPCHK(prf_launch_lit_upper(st, (uint8_t *)d_seq.p, total, (u64 *)d_ctr.p));
-    HIPCHK(prf_launch_int_trim(st, (const uint8_t *)d_seq.p, (const u64 *)d_base.p, (const u64 *)d_chunks.p, n_chunks, (u64 *)d_fl.p));
-    launches += 2;
-    u64 h_ctr[8];
-    HIPCHK(hipMemcpyAsync(h_ctr, d_ctr.p, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(fl.data(), d_fl.p, fl.size() * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (h_ctr[0] != ~0ull) {
-        const u64 at = h_ctr[0];
-        u32 ci = (u32)(std::upper_bound(seq_base.begin(), seq_base.begin() + n_seq, at) - seq_base.begin()) - 1;
-        return fail(PRF_ESYMBOL, "unsupported symbol at contig %u position %llu: only letters are accepted (A, C, G, T, N and -- as "
-                    "ordinary symbols, like the reference -- any other letter, in either case)", ci, (unsigned long long)(at - seq_base[ci]));
-    }
-
-    // lanes in (sequence, k, chunk) order; the chunks cut the trimmed sequence
-    std::vector<u32> lane0(std::max<u32>(1, n_seq)), nch(std::max<u32>(1, n_seq));
-    u64 n_lanes64 = 0;
-    for (u32 i = 0; i < n_seq; i++) {
-        const u64 n_trim = fl[2 * i] == ~0ull ? 0 : fl[2 * i + 1] - fl[2 * i];
-        const u64 nc = chunk ? std::max<u64>(1, (n_trim + chunk - 1) / chunk) : 1;
-        if (n_lanes64 + nc * nk > 0x7fffffffull) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: too many (sequence, motif size, chunk) lanes");
-        lane0[i] = (u32)n_lanes64;
-        nch[i] = (u32)nc;
-        n_lanes64 += nc * nk;
-    }
-    const u32 n_lanes = (u32)n_lanes64;
-    std::vector<prf_ilane> lanes(std::max<u32>(1, n_lanes));
-    std::vector<u64> cand_cap(n_lanes);
-    u64 memo_total = 0;
-    for (u32 i = 0, li = 0; i < n_seq; i++) {
-        const u64 len = contigs[i].len, reach = chunk ? std::min<u64>(len, chunk) : len;
-        for (u32 j = 0; j < nk; j++)
-            for (u32 ch = 0; ch < nch[i]; ch++, li++) {
-                prf_ilane &ln = lanes[li];
-                ln.seq = i;
-                ln.k = kmin + j;
-                ln.seq_base = seq_base[i];
-                ln.chunk = ch;
-                ln.kslot = i * nk + j;
-                ln.lo = (u64)ch * chunk;
-                ln.hi = chunk ? (u64)(ch + 1) * chunk : (u64)INT64_MAX;
-                ln.cand_off = ln.cand_cap = ln.ep_off = ln.ep_cap = 0;
-                ln.memo_slots = memo_stride ? std::min<u64>(memo_slots, reach / memo_stride + 1) : 0;
-                ln.memo_off = memo_total;
-                memo_total += ln.memo_slots;
-            }
-    }
-    if ((rc = d_lanes.alloc(lanes.size() * sizeof(prf_ilane))) || (rc = d_cnt.alloc(8 * (size_t)std::max<u32>(1, n_lanes))) ||
-        (rc = d_end.alloc(4 * (size_t)std::max<u32>(1, n_lanes))) || (rc = d_first_end.alloc(4 * (size_t)std::max<u32>(1, n_seq * nk))) ||
-        (rc = d_memo.alloc(memo_total * sizeof(prf_imemo))))
-        return rc;
-    if (chunk) {
-        // every episode of a lane lands on a boundary of its chunk (the first lane's first one on position 0) and lists at most
-        // one candidate: counting the boundaries sizes both arrays so that the walk runs once
-        if ((rc = d_bcount.alloc(8 * (size_t)std::max<u32>(1, n_lanes)))) return rc;
-        HIPCHK(hipMemcpyAsync(d_lanes.p, lanes.data(), lanes.size() * sizeof(prf_ilane), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(d_bcount.p, 0, 8 * (size_t)std::max<u32>(1, n_lanes), st));
-        HIPCHK(prf_launch_int_bound(st, (const uint8_t *)d_seq.p, (const prf_ilane *)d_lanes.p, n_lanes, (const u64 *)d_fl.p, (u64 *)d_bcount.p));
-        launches++;
-        if (n_lanes) HIPCHK(hipMemcpyAsync(cand_cap.data(), d_bcount.p, 8 * (size_t)n_lanes, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (u32 li = 0; li < n_lanes; li++) cand_cap[li] += 1;
-    } else {
-        // about one candidate per five positions on random sequence (every episode that jumps back ends in one): room for one per
-        // four, so that the walk usually runs once
-        for (u32 li = 0; li < n_lanes; li++) cand_cap[li] = contigs[lanes[li].seq].len / 4 + 16;
-    }
-    u64 ep_total = 0;
-    for (u32 li = 0; li < n_lanes; li++) {
-        prf_ilane &ln = lanes[li];
-        // episodes land at strictly increasing positions: at most len of them; past ep_cap they are not recorded
-        ln.ep_cap = !ln.memo_slots ? 0 : chunk ? cand_cap[li] : contigs[ln.seq].len / 4 + 64;
-        ln.ep_off = ep_total;
-        ep_total += ln.ep_cap;
-    }
-    if ((rc = d_eps.alloc(ep_total * 4))) return rc;
-
-    std::vector<u64> cnt(std::max<u32>(1, n_lanes));
-    std::vector<u32> lane_end(std::max<u32>(1, n_lanes));
-    for (int attempt = 0;; attempt++) {
-        u64 cand_total = 0;
-        for (u32 li = 0; li < n_lanes; li++) {
-            lanes[li].cand_off = cand_total;
-            lanes[li].cand_cap = cand_cap[li];
-            cand_total += cand_cap[li];
-        }
-        if ((rc = d_cands.alloc(cand_total * sizeof(prf_icand)))) return rc;
-        HIPCHK(hipMemcpyAsync(d_lanes.p, lanes.data(), lanes.size() * sizeof(prf_ilane), hipMemcpyHostToDevice, st));
-        if (memo_total) HIPCHK(hipMemsetAsync(d_memo.p, 0xFF, memo_total * sizeof(prf_imemo), st));  // no state has pos ~0
-        HIPCHK(hipMemsetAsync(d_first_end.p, 0xFF, 4 * (size_t)std::max<u32>(1, n_seq * nk), st));
-        HIPCHK(hipMemsetAsync((u64 *)d_ctr.p + 1, 0, 7 * 8, st));
-        HIPCHK(hipEventRecord(c->ev[1], st));
-        HIPCHK(prf_launch_int_walk(st, (const uint8_t *)d_seq.p, (const prf_ilane *)d_lanes.p, n_lanes, (const u64 *)d_fl.p, min_repeats,
-                                   min_span, max_int, memo_stride, (prf_icand *)d_cands.p, (u64 *)d_cnt.p, (u32 *)d_end.p,
-                                   chunk ? (u32 *)d_first_end.p : nullptr, (prf_imemo *)d_memo.p, (u32 *)d_eps.p, (u64 *)d_ctr.p + 1));
-        HIPCHK(hipEventRecord(c->ev[2], st));
-        launches++;
-        HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, 8 * (size_t)n_lanes, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(lane_end.data(), d_end.p, 4 * (size_t)n_lanes, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(h_ctr, d_ctr.p, 8 * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        bool over = false;
-        for (u32 li = 0; li < n_lanes; li++) {
-            if (cnt[li] > (u64)0x3fffffff) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: more than 2^30 candidates on one lane");
-            if (cnt[li] > cand_cap[li]) { over = true; cand_cap[li] = cnt[li]; }
-        }
-        if (!over) break;
-        if (attempt >= 1) return fail(PRF_EHIP, "prf_scan_interrupted: the candidate counts changed between two runs");
-    }
-    // the chunks behind the first lane of a (sequence, k) that ended start on landings the walk never reaches: dropped
-    u64 dropped = 0;
-    for (u32 i = 0; i < n_seq; i++)
-        for (u32 j = 0; j < nk; j++) {
-            const u32 l0 = lane0[i] + j * nch[i];
-            u32 e = 0;
-            while (e < nch[i] && !lane_end[l0 + e]) e++;
-            if (e == nch[i]) return fail(PRF_EHIP, "prf_scan_interrupted: no lane of contig %u, motif size %u reached the end", i, kmin + j);
-            for (u32 ch = e + 1; ch < nch[i]; ch++) cnt[l0 + ch] = 0;
-            dropped += nch[i] - 1 - e;
-        }
-    float walk_ms = 0;
-    HIPCHK(hipEventElapsedTime(&walk_ms, c->ev[1], c->ev[2]));
-
-    // emission: one lane per sequence, a hash of the emitted (start, end) per sequence
-    std::vector<u64> hoff(std::max<u32>(1, n_seq)), hsize(std::max<u32>(1, n_seq));
-    u64 htotal = 0, cand_sum = 0;
-    for (u32 i = 0; i < n_seq; i++) {
-        u64 cs = 0;
-        for (u32 l = 0; l < nk * nch[i]; l++) cs += cnt[(size_t)lane0[i] + l];
-        cand_sum += cs;
-        u64 sz = 16;
-        while (sz < 2 * cs) sz <<= 1;
-        hoff[i] = htotal;
-        hsize[i] = sz;
-        htotal += sz;
-    }
-    dev_buf d_hoff, d_hsize, d_keys, d_rows, d_sorted, d_scratch, d_lane0, d_nch;
-    if ((rc = d_lane0.alloc(lane0.size() * 4)) || (rc = d_nch.alloc(nch.size() * 4)) || (rc = d_hoff.alloc(hoff.size() * 8)) || (rc = d_hsize.alloc(hsize.size() * 8)) || (rc = d_keys.alloc(htotal * 16)) ||
-        (rc = d_rows.alloc(cand_sum * sizeof(prf_ihit_dev))) || (rc = d_sorted.alloc(cand_sum * sizeof(prf_ihit_dev))) ||
-        (rc = d_scratch.alloc(prf_int_sort_scratch_bytes(cand_sum))))
-        return rc;
-    HIPCHK(hipMemcpyAsync(d_lane0.p, lane0.data(), lane0.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_nch.p, nch.data(), nch.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_hoff.p, hoff.data(), hoff.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_hsize.p, hsize.data(), hsize.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_keys.p, 0, htotal * 16, st));
-    HIPCHK(hipMemsetAsync((u64 *)d_ctr.p + 5, 0, 8, st));
-    HIPCHK(hipEventRecord(c->ev[2], st));
-    HIPCHK(prf_launch_int_emit(st, (const prf_ilane *)d_lanes.p, nk, n_seq, (const u32 *)d_lane0.p, (const u32 *)d_nch.p,
-                               (const u32 *)d_end.p, (const prf_icand *)d_cands.p, (const u64 *)d_cnt.p,
-                               (const u64 *)d_fl.p, (const u64 *)d_hoff.p, (const u64 *)d_hsize.p, (u64 *)d_keys.p,
-                               (prf_ihit_dev *)d_rows.p, (u64 *)d_ctr.p + 5));
-    launches++;
-    u64 n_rows = 0;
-    HIPCHK(hipMemcpyAsync(&n_rows, (u64 *)d_ctr.p + 5, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (n_rows > cand_sum) return fail(PRF_EHIP, "prf_scan_interrupted: emission returned %llu rows for %llu candidates",
-                                       (unsigned long long)n_rows, (unsigned long long)cand_sum);
-    HIPCHK(prf_int_sort_rows(st, (const prf_ihit_dev *)d_rows.p, n_rows, (prf_ihit_dev *)d_sorted.p, d_scratch.p));
-    if (n_rows) launches += 11;
-    HIPCHK(hipEventRecord(c->ev[3], st));
-    prf_ihit *rows = nullptr;
-    if (out && n_rows) {
-        rows = (prf_ihit *)malloc(n_rows * sizeof(prf_ihit));
-        if (!rows) return fail(PRF_ENOMEM, "prf_scan_interrupted: cannot allocate %llu rows", (unsigned long long)n_rows);
-        const hipError_t e = hipMemcpyAsync(rows, d_sorted.p, n_rows * sizeof(prf_ihit), hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) { free(rows); HIPCHK(e); }
-    }
-    {
-        const hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { free(rows); HIPCHK(e); }
-    }
-    float all_ms = 0, emit_ms = 0;
-    HIPCHK(hipEventElapsedTime(&all_ms, c->ev[0], c->ev[3]));
-    HIPCHK(hipEventElapsedTime(&emit_ms, c->ev[2], c->ev[3]));
-    c->last.nhits = 0;  // the rows of this lane are handed over on the host only
-    c->last.rows = nullptr;
-    if (out) { out->rows = rows; out->n = rows ? n_rows : 0; }
-    if (stats) {
-        memset(stats, 0, sizeof *stats);
-        stats->scan_ms = all_ms;
-        stats->phase1_ms = walk_ms;
-        stats->phase2_ms = emit_ms;
-        stats->positions = positions;
-        stats->packed_bytes = positions;  // this lane reads the bytes themselves
-        stats->n_candidates = cand_sum;
-        stats->n_hits = n_rows;
-        stats->n_launches = launches;
-        stats->path = 3;
-        stats->sorted_on_device = 1;
-    }
-    if (counters_out) {
-        counters_out[0] = h_ctr[1];  // walk steps
-        counters_out[1] = h_ctr[2];  // memo lookups
-        counters_out[2] = h_ctr[3];  // memo hits
-        counters_out[3] = h_ctr[4];  // recorded episodes
-        if (chunk) {
-            counters_out[4] = n_lanes;
-            counters_out[5] = dropped;
-        }
-    }
-    return PRF_OK;
-}
-
-int prf_scan_interrupted_ex(prf_ctx *c, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax, uint32_t min_repeats,
-                            uint32_t min_span, uint32_t max_interruptions, uint32_t memo_stride, uint64_t memo_slots, prf_ihits *out,
-                            prf_scan_stats *stats, uint64_t *counters) {
-    return guarded("prf_scan_interrupted", [&] {
-        return interrupted_impl(c, contigs, n_contigs, kmin, kmax, min_repeats, min_span, max_interruptions, memo_stride, memo_slots, 0,
-                                out, stats, counters);
-    });
-}
-
-int prf_scan_interrupted_chunked(prf_ctx *c, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax, uint32_t min_repeats,
-                                 uint32_t min_span, uint32_t max_interruptions, uint32_t memo_stride, uint64_t memo_slots, uint64_t chunk,
-                                 prf_ihits *out, prf_scan_stats *stats, uint64_t *counters) {
-    return guarded("prf_scan_interrupted_chunked", [&] {
-        if (counters && !chunk) counters[4] = counters[5] = 0;
-        const int rc = interrupted_impl(c, contigs, n_contigs, kmin, kmax, min_repeats, min_span, max_interruptions, memo_stride,
-                                        memo_slots, chunk, out, stats, counters);
-        if (rc == PRF_OK && counters && !chunk) counters[4] = (uint64_t)n_contigs * (kmax - kmin + 1);  // one lane each, none dropped
-        return rc;
-    });
-}
-
-int prf_scan_interrupted(prf_ctx *c, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax, uint32_t min_repeats,
-                         uint32_t min_span, uint32_t max_interruptions, prf_ihits *out, prf_scan_stats *stats) {
-    return prf_scan_interrupted_chunked(c, contigs, n_contigs, kmin, kmax, min_repeats, min_span, max_interruptions, PRF_MEMO_STRIDE,
-                                        PRF_MEMO_SLOTS, PRF_INT_CHUNK, out, stats, nullptr);
-}
-
-void prf_free_ihits(prf_ihits *hits) {
-    if (!hits) return;
-    free(hits->rows);
-    hits->rows = nullptr;
-    hits->n = 0;
 }
 
 // ---- pipelined scans: enqueue now, collect later (at most two in flight) ----

@@ -1,4 +1,5 @@
-// prf_host.h -- launch wrappers shared between the kernel translation units and api.cpp.
+// prf_host.h -- launch wrappers shared between the kernel translation units and the host ones that call them (api.cpp,
+// interrupted.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -85,17 +86,42 @@ struct prf_ihit_dev {         // = prf_ihit
 };
 hipError_t prf_launch_int_trim(hipStream_t s, const uint8_t *buf, const u64 *seq_base, const u64 *chunks, u32 n_chunks,
                                u64 *first_last);
-// counters[0..3] += steps, memo lookups, memo hits, recorded episodes; lane_end[li] = the walk ended in lane li.
+// what the walk writes and the emission reads
+struct prf_int_lanes {
+    const prf_ilane *lanes;
+    u32 n_lanes;
+    const u64 *first_last;    // per sequence: first / one-past-last position that is not N (first == ~0: nothing but N)
+    prf_icand *cands;         // the lanes' candidate lists (prf_ilane::cand_off, cand_cap)
+    u64 *cand_cnt;            // per lane: candidates the walk found (above cand_cap: the list holds the first cand_cap)
+    u32 *lane_end;            // per lane: the walk ended in this lane
+};
+// counters[0..3] += steps, memo lookups, memo hits, recorded episodes.
 // first_end == NULL: one lane per thread (one chunk per (sequence, k)).  Otherwise one lane per wave, and first_end[kslot]
 // (set to ~0 by the caller) receives the first chunk of each (sequence, k) whose lane ended.
-hipError_t prf_launch_int_walk(hipStream_t s, const uint8_t *buf, const prf_ilane *lanes, u32 n_lanes, const u64 *first_last,
-                               u32 min_repeats, u32 min_span, u32 max_int, u32 stride, prf_icand *cands, u64 *cand_cnt, u32 *lane_end,
-                               u32 *first_end, prf_imemo *memo, u32 *eps, u64 *counters);
+struct prf_int_walk_args {
+    prf_int_lanes l;
+    const uint8_t *buf;
+    u32 min_repeats, min_span, max_int, stride;
+    u32 *first_end;
+    prf_imemo *memo;
+    u32 *eps;
+    u64 *counters;
+};
+hipError_t prf_launch_int_walk(hipStream_t s, const prf_int_walk_args &a);
 // bcount[li] += the boundaries in lane li's [lo, hi): with one more for position 0, an upper bound of its episodes and candidates
 hipError_t prf_launch_int_bound(hipStream_t s, const uint8_t *buf, const prf_ilane *lanes, u32 n_lanes, const u64 *first_last,
                                 u64 *bcount);
-hipError_t prf_launch_int_emit(hipStream_t s, const prf_ilane *lanes, u32 nk, u32 n_seq, const u32 *lane0, const u32 *n_chunks,
-                               const u32 *lane_end, const prf_icand *cands, const u64 *cand_cnt, const u64 *first_last, const u64 *hash_off, const u64 *hash_size, u64 *keys, prf_ihit_dev *rows,
-                               u64 *row_cnt);
+// one thread per sequence: its lanes are lane0[s] + j * n_chunks[s] + c for motif size j of nk and chunk c; its hash of emitted
+// (start, end) is keys[2 * hash_off[s] ..] with hash_size[s] slots (a power of two, zeroed by the caller); *row_cnt += its rows
+struct prf_int_emit_args {
+    prf_int_lanes l;
+    u32 nk, n_seq;
+    const u32 *lane0, *n_chunks;
+    const u64 *hash_off, *hash_size;
+    u64 *keys;
+    prf_ihit_dev *rows;
+    u64 *row_cnt;
+};
+hipError_t prf_launch_int_emit(hipStream_t s, const prf_int_emit_args &a);
 size_t prf_int_sort_scratch_bytes(u64 n);
 hipError_t prf_int_sort_rows(hipStream_t s, const prf_ihit_dev *rows, u64 n, prf_ihit_dev *out, void *scratch);

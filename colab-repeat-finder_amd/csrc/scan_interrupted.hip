@@ -306,38 +306,38 @@ __global__ void __launch_bounds__(64) prf_int_emit_kernel(const prf_ilane *__res
         prf_icand last{};
         bool ended = false;
         for (u32 ch = 0; ch < nc && !ended; ch++) {
-        const u32 li = lane0[s] + j * nc + ch;
-        const prf_ilane ln = lanes[li];
-        const u64 cnt = cand_cnt[li];
-        const i64 k = ln.k;
-        ended = lane_end[li] != 0;
-        for (u64 i = 0; i < cnt; i++) {
-            const prf_icand c = cands[ln.cand_off + i];
-            // a candidate equal to the one before it can never change the result
-            if (have_last && c.start == last.start && c.end == last.end && c.mask == last.mask) continue;
-            last = c;
-            have_last = true;
-            if (c.homo) continue;
-            if (have_prev && (i64)(c.end - prev_end) < k) continue;
-            u64 slot = key_hash(c.start, c.end) & hmask;
-            bool seen = false;
-            for (;;) {
-                const u64 e = tab[2 * slot + 1];
-                if (e == 0) break;  // empty (every end is >= 1)
-                if (e == c.end && tab[2 * slot] == c.start) {
-                    seen = true;
-                    break;
+            const u32 li = lane0[s] + j * nc + ch;
+            const prf_ilane ln = lanes[li];
+            const u64 cnt = cand_cnt[li];
+            const i64 k = ln.k;
+            ended = lane_end[li] != 0;
+            for (u64 i = 0; i < cnt; i++) {
+                const prf_icand c = cands[ln.cand_off + i];
+                // a candidate equal to the one before it can never change the result
+                if (have_last && c.start == last.start && c.end == last.end && c.mask == last.mask) continue;
+                last = c;
+                have_last = true;
+                if (c.homo) continue;
+                if (have_prev && (i64)(c.end - prev_end) < k) continue;
+                u64 slot = key_hash(c.start, c.end) & hmask;
+                bool seen = false;
+                for (;;) {
+                    const u64 e = tab[2 * slot + 1];
+                    if (e == 0) break;  // empty (every end is >= 1)
+                    if (e == c.end && tab[2 * slot] == c.start) {
+                        seen = true;
+                        break;
+                    }
+                    slot = (slot + 1) & hmask;
                 }
-                slot = (slot + 1) & hmask;
+                if (seen) continue;
+                tab[2 * slot] = c.start;
+                tab[2 * slot + 1] = c.end;
+                const u64 at = atomicAdd(row_cnt, 1ull);
+                rows[at] = prf_ihit_dev{c.start + head, c.end + head, (u32)k, s, c.mask};
+                prev_end = c.end;
+                have_prev = true;
             }
-            if (seen) continue;
-            tab[2 * slot] = c.start;
-            tab[2 * slot + 1] = c.end;
-            const u64 at = atomicAdd(row_cnt, 1ull);
-            rows[at] = prf_ihit_dev{c.start + head, c.end + head, (u32)k, s, c.mask};
-            prev_end = c.end;
-            have_prev = true;
-        }
         }
     }
 }
@@ -400,16 +400,16 @@ hipError_t prf_launch_int_trim(hipStream_t st, const uint8_t *buf, const u64 *se
     return hipGetLastError();
 }
 
-hipError_t prf_launch_int_walk(hipStream_t st, const uint8_t *buf, const prf_ilane *lanes, u32 n_lanes, const u64 *first_last,
-                               u32 min_repeats, u32 min_span, u32 max_int, u32 stride, prf_icand *cands, u64 *cand_cnt, u32 *lane_end,
-                               u32 *first_end, prf_imemo *memo, u32 *eps, u64 *counters) {
-    if (!n_lanes) return hipSuccess;
-    if (first_end)
-        hipLaunchKernelGGL(prf_int_walk_chunk_kernel, dim3(n_lanes), dim3(64), 0, st, buf, lanes, n_lanes, first_last, min_repeats,
-                           min_span, max_int, stride, cands, cand_cnt, lane_end, first_end, memo, eps, counters);
+hipError_t prf_launch_int_walk(hipStream_t st, const prf_int_walk_args &a) {
+    const prf_int_lanes &l = a.l;
+    if (!l.n_lanes) return hipSuccess;
+    if (a.first_end)
+        hipLaunchKernelGGL(prf_int_walk_chunk_kernel, dim3(l.n_lanes), dim3(64), 0, st, a.buf, l.lanes, l.n_lanes, l.first_last,
+                           a.min_repeats, a.min_span, a.max_int, a.stride, l.cands, l.cand_cnt, l.lane_end, a.first_end, a.memo, a.eps,
+                           a.counters);
     else
-        hipLaunchKernelGGL(prf_int_walk_kernel, dim3((n_lanes + 63) / 64), dim3(64), 0, st, buf, lanes, n_lanes, first_last, min_repeats,
-                           min_span, max_int, stride, cands, cand_cnt, lane_end, memo, eps, counters);
+        hipLaunchKernelGGL(prf_int_walk_kernel, dim3((l.n_lanes + 63) / 64), dim3(64), 0, st, a.buf, l.lanes, l.n_lanes, l.first_last,
+                           a.min_repeats, a.min_span, a.max_int, a.stride, l.cands, l.cand_cnt, l.lane_end, a.memo, a.eps, a.counters);
     return hipGetLastError();
 }
 
@@ -420,12 +420,11 @@ hipError_t prf_launch_int_bound(hipStream_t st, const uint8_t *buf, const prf_il
     return hipGetLastError();
 }
 
-hipError_t prf_launch_int_emit(hipStream_t st, const prf_ilane *lanes, u32 nk, u32 n_seq, const u32 *lane0, const u32 *n_chunks,
-                               const u32 *lane_end, const prf_icand *cands, const u64 *cand_cnt, const u64 *first_last, const u64 *hash_off, const u64 *hash_size, u64 *keys, prf_ihit_dev *rows,
-                               u64 *row_cnt) {
-    if (!n_seq) return hipSuccess;
-    hipLaunchKernelGGL(prf_int_emit_kernel, dim3((n_seq + 63) / 64), dim3(64), 0, st, lanes, nk, n_seq, lane0, n_chunks, lane_end, cands, cand_cnt,
-                       first_last, hash_off, hash_size, keys, rows, row_cnt);
+hipError_t prf_launch_int_emit(hipStream_t st, const prf_int_emit_args &a) {
+    const prf_int_lanes &l = a.l;
+    if (!a.n_seq) return hipSuccess;
+    hipLaunchKernelGGL(prf_int_emit_kernel, dim3((a.n_seq + 63) / 64), dim3(64), 0, st, l.lanes, a.nk, a.n_seq, a.lane0, a.n_chunks,
+                       l.lane_end, l.cands, l.cand_cnt, l.first_last, a.hash_off, a.hash_size, a.keys, a.rows, a.row_cnt);
     return hipGetLastError();
 }
 
