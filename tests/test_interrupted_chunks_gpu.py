@@ -17,6 +17,9 @@ pytestmark = pytest.mark.gpu
 # MI355X; the limit is about three times the former.  The one-lane engine did not finish it within 200 s.
 LARGE_LIMIT_S = 45.0
 LARGE_ROWS = 143_877          # the CPU model's row count for this exact input (1 434 s)
+# SHA-256 of the CPU model's rows for this exact input (interrupted_model.detect, stride 8, 2^22 slots; 1 017 s on a CPU)
+# as _rows_digest() lays them out.  Never taken from a GPU's output.
+LARGE_SHA256 = "e7d2d5911e727b2998eb3f0b271d84057fe58de9da113d82a900562d169a9dc5"
 
 
 @pytest.fixture(scope="module")
@@ -53,6 +56,14 @@ def _random_with_repeats(n, seed):
         p = rng.randrange(n - len(rep))
         s[p:p + len(rep)] = rep
     return bytes(s)
+
+
+def _rows_digest(rows):
+    """SHA-256 of the rows as little-endian 64-bit (contig, start, end, k, nmask), row after row."""
+    import hashlib
+    import numpy as np
+    a = np.stack([rows[f].astype("<u8") for f in ("contig", "start", "end", "k", "nmask")], axis=1)
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 @pytest.mark.parametrize("chunk", [32, 7])
@@ -183,7 +194,8 @@ def test_cli_chunk_option_writes_the_same_bed(ctx, tmp_path, monkeypatch):
 
 def test_chr22_sized_standin_finishes(ctx):
     """The reference's only benchmark of this mode, on the stand-in tools/interrupted_timing.py builds by default: the row count
-    the CPU model found, the same rows for two chunk sizes, each call within LARGE_LIMIT_S.
+    and the digest of the rows (contig, start, end, k, nmask) the CPU model found, the same rows for two chunk sizes,
+    each call within LARGE_LIMIT_S.
 
     Measured on an MI355X: see DESIGN 9.5."""
     import numpy as np
@@ -199,6 +211,7 @@ def test_chr22_sized_standin_finishes(ctx):
         print(f"chunk {chunk}: {wall:.2f} s (device {stats.scan_ms / 1e3:.2f} s: walk {stats.phase1_ms / 1e3:.2f}, emission + sort "
               f"{stats.phase2_ms / 1e3:.2f}), {len(rows)} rows, {ctr['lanes']} lanes, {ctr['dropped_lanes']} dropped")
         assert len(rows) == LARGE_ROWS
+        assert _rows_digest(rows) == LARGE_SHA256, f"chunk {chunk}: the rows differ from the CPU model's"
         assert wall < LARGE_LIMIT_S, f"chunk {chunk}: {wall:.1f} s"
         assert ctr["lanes"] == C.n_chunks(length - min(10_510_000, length // 5) - min(10_000, length // 100), chunk) * 6
         seen.append(rows)

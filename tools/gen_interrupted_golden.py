@@ -7,6 +7,16 @@ runs the driver the project pins: upper-case, N-trimming of the whole
 ONE shared dict, `while t.advance(): pass; t.done()`, rows = sorted(out.items()) shifted by the trimmed head.
 
     python3 tools/gen_interrupted_golden.py --reference PATH_TO_REFERENCE_CHECKOUT [--cases 3200] [--seed 9]
+    python3 tools/gen_interrupted_golden.py --reference PATH_TO_REFERENCE_CHECKOUT --long [--seed 17] [--jobs 4]
+
+--long writes tests/golden/interrupted_long.jsonl.gz instead: a few dozen cases of 3-40 kb (the short fixture stops at 600
+positions) in the same format and through the same driver, from one seed (long_cases() lists them): random ACGT of 5-40 kb with
+and without planted interrupted repeats, 20 kb of two- and three-letter sequence, planted units of 16-64 under k 16-64 and 60-64
+(one unit of exactly 64 with its interruption at phase 63), max_interruptions 4, 6, 8 and 64, min_repeats 2 and 5, min_span 1 and
+100, and N blocks, N ends, lower case and IUPAC letters at 10 kb.  The reference rows take minutes (--jobs processes; the bytes do
+not depend on it).  Before it writes, the tool checks with the project's model (tests/interrupted_model.py) that one (sequence, k)
+of a low-complexity case lists more candidates than len / 4 + 16 and one has more episodes than len / 4 + 64 (the room the one-lane
+engine gives a lane), and that the 64-long unit is reported with phase 63 varying.
 
 Each line: {"tag", "seq", "settings": {min_motif_size, max_motif_size, min_repeats, min_span, max_interruptions},
 "rows": [[start, end, motif], ...]} -- the motif with N at the phases that were allowed to vary.
@@ -18,7 +28,9 @@ import os
 import random
 import sys
 
-OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "interrupted.jsonl.gz")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.path.join(ROOT, "tests", "golden", "interrupted.jsonl.gz")
+LONG_OUT = os.path.join(ROOT, "tests", "golden", "interrupted_long.jsonl.gz")
 
 
 def reference_rows(RepeatTracker, seq, kmin, kmax, min_repeats, min_span, max_interruptions):
@@ -100,16 +112,162 @@ def make_case(rng, i):
             "settings": {"min_motif_size": kmin, "max_motif_size": kmax, "min_repeats": r, "min_span": span, "max_interruptions": m}}
 
 
+# ---- the long fixture (--long) ----
+
+def plant_into(rng, s, count, unit_lens, copies, changes, alphabet="ACGT"):
+    """Overwrite `count` stretches of the list s with planted interrupted repeats."""
+    for _ in range(count):
+        rep = planted(rng, rng.randint(*unit_lens), rng.randint(*copies), rng.randint(*changes), alphabet)
+        p = rng.randrange(len(s) - len(rep))
+        s[p:p + len(rep)] = rep
+
+
+def unit64_phase63(rng):
+    """Four copies of a 64-long unit, the third with its last base changed, behind eight bases that match nothing 64 further on
+    (no run of k = 64 starts early): the mismatch comes at run 127, phase 63."""
+    unit = random_seq(rng, 64, "ACGT")
+
+    def other(ch):
+        return "ACGT"["ACGT".index(ch) ^ 1]
+    return "".join(other(ch) for ch in unit[56:]) + unit * 2 + unit[:63] + other(unit[63]) + unit
+
+
+def long_cases(seed):
+    """[{"tag", "seq", "settings"}]: the settings come from a small palette (17 of them), so that a test can hand all cases of
+    one setting to one call."""
+    rng = random.Random(seed)
+    cases = []
+
+    def add(tag, seq, kmin, kmax, r, span, m):
+        cases.append({"tag": tag, "seq": seq, "settings": {"min_motif_size": kmin, "max_motif_size": kmax, "min_repeats": r,
+                                                          "min_span": span, "max_interruptions": m}})
+
+    def acgt(n, plant, unit_lens=(1, 8), copies=(3, 20), changes=(0, 3)):
+        s = list(random_seq(rng, n, "ACGT"))
+        if plant:
+            plant_into(rng, s, n // 1000, unit_lens, copies, changes)
+        return "".join(s)
+
+    a, b, c, d = (1, 6, 3, 9, 1), (2, 8, 2, 5, 2), (2, 8, 3, 9, 2), (1, 6, 2, 5, 3)
+    for tag, n, plant, st in (("random", 5_000, False, a), ("random_planted", 5_000, True, b), ("random", 5_000, False, b),
+                              ("random", 10_000, False, c), ("random_planted", 10_000, True, d), ("random", 20_000, False, a),
+                              ("random_planted", 20_000, True, a), ("random_planted", 20_000, True, c), ("random", 20_000, False, d),
+                              ("random_planted", 40_000, True, a)):
+        add(tag, acgt(n, plant), *st)
+    # two and three letters: nearly every position closes a candidate (the one-lane engine's candidate and episode room overflow)
+    for alphabet, st in (("AC", (1, 6, 2, 5, 1)), ("AT", (1, 6, 2, 5, 1)), ("AAC", (1, 6, 2, 5, 1)), ("AC", (1, 6, 3, 9, 2))):
+        add("low_complexity", random_seq(rng, 20_000, alphabet), *st)
+    # On random two-letter sequence a quarter of the positions are boundaries of k = 2 (a mismatch right behind a match), and each
+    # becomes an episode with a candidate: len / 4 on average, which is the room.  Take the first of the draws that lies far enough
+    # above the average to overflow both (about one in forty does).
+    for t in range(4000):
+        seq = random_seq(random.Random(seed * 4000 + t), 20_000, "AC")
+        if sum(seq[q - 1] == seq[q + 1] and seq[q] != seq[q + 2] for q in range(1, len(seq) - 2)) > len(seq) // 4 + 80:
+            break
+    else:
+        raise RuntimeError("none of 4000 draws of 20 kb of AC has more than len / 4 + 80 boundaries of k = 2")
+    add("low_complexity", seq, 1, 6, 2, 5, 1)
+    # planted units of 16-64 under large k
+    for n, st, with64 in ((3_000, (16, 64, 2, 5, 1), True), (5_000, (16, 64, 3, 9, 2), False), (10_000, (16, 64, 2, 5, 3), False),
+                          (5_000, (60, 64, 2, 5, 1), True), (3_000, (60, 64, 3, 9, 3), True), (10_000, (60, 64, 2, 5, 2), True)):
+        s = list(random_seq(rng, n, "ACGT"))
+        plant_into(rng, s, n // 500, (max(16, st[0]), 64), (2, 5), (0, 4))
+        if with64:
+            rep = unit64_phase63(rng)
+            p = rng.randrange(n - len(rep))
+            s[p:p + len(rep)] = rep
+        add("large_k_unit64" if with64 else "large_k", "".join(s), *st)
+    # more interruptions than the short fixture has (m >= k for every k of the range in the last two)
+    for n, m, r, span in ((5_000, 4, 3, 9), (5_000, 6, 3, 9), (10_000, 8, 2, 5), (5_000, 64, 3, 9)):
+        add("many_interruptions", acgt(n, True, changes=(0, 8)), 1, 8, r, span, m)
+    # thresholds: r 2 and 5, span 1, and a span that binds instead of r * k
+    for n, st in ((10_000, (2, 8, 2, 1, 1)), (5_000, (2, 8, 5, 1, 2)), (10_000, (2, 8, 3, 100, 2)), (5_000, (1, 6, 5, 100, 1)),
+                  (5_000, (1, 6, 2, 100, 2))):
+        add("thresholds", acgt(n, True, copies=(3, 60)), *st)
+    # N inside and at both ends, lower case, IUPAC letters (ordinary symbols for this tracker), at 10 kb
+    body = acgt(10_000, True)
+    add("n_block", "N" * 40 + body[:4_000] + "N" * 300 + body[4_300:9_900] + "N" * 25, *a)
+    body = acgt(10_000, True).lower()
+    add("lower_n_block", body[:7_000] + "n" * 500 + body[7_500:], *b)
+    s = list(acgt(10_000, True))
+    for _ in range(400):
+        s[rng.randrange(len(s))] = rng.choice("RYKMSWBDHVN")
+    plant_into(rng, s, 5, (1, 6), (3, 12), (0, 2), "ACGTRYN")
+    add("iupac", "".join(s), *c)
+    s = list(acgt(10_000, True))
+    for _ in range(200):
+        s[rng.randrange(len(s))] = rng.choice("RYKMSWNacgtn")
+    s[2_000:2_150] = "N" * 150
+    add("n_ends_lower_iupac", "nnNN" + "".join(s) + "Nn", *d)
+    return cases
+
+
+def check_long_cases(cases):
+    """What the fixture is for, checked with the project's model before the reference runs."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import interrupted_model as M
+    over_cands = over_eps = phase63 = False
+    for c in cases:
+        st = c["settings"]
+        if c["tag"] == "low_complexity":
+            s, _head = M.trim(c["seq"])
+            for k in range(st["min_motif_size"], st["max_motif_size"] + 1):
+                w = M.walk(s, k, st["min_repeats"], st["min_span"], st["max_interruptions"], stride=8, slots=1 << 16)
+                over_cands |= len(w.cands) > len(c["seq"]) // 4 + 16
+                over_eps |= len(w.landings) + 1 > len(c["seq"]) // 4 + 64
+        if c["tag"] == "large_k_unit64":
+            rows = M.detect(c["seq"], st["min_motif_size"], st["max_motif_size"], st["min_repeats"], st["min_span"], st["max_interruptions"],
+                            stride=8, slots=1 << 16)
+            phase63 |= any(k == 64 and (mask >> 63) & 1 for _a, _b, k, mask, _motif in rows)
+    assert phase63, "no case reports a k = 64 row with phase 63 varying"
+    assert over_cands, "no (sequence, k) of a low-complexity case has more than len / 4 + 16 candidates"
+    assert over_eps, "no (sequence, k) of a low-complexity case has more than len / 4 + 64 episodes"
+
+
+_TRACKER = None
+
+
+def _long_rows(case):
+    st = case["settings"]
+    return reference_rows(_TRACKER, case["seq"], st["min_motif_size"], st["max_motif_size"], st["min_repeats"], st["min_span"],
+                          st["max_interruptions"])
+
+
+def write_long(RepeatTracker, seed, out, jobs):
+    global _TRACKER
+    import multiprocessing
+    _TRACKER = RepeatTracker
+    cases = long_cases(seed)
+    check_long_cases(cases)
+    if jobs > 1:
+        with multiprocessing.get_context("fork").Pool(jobs) as pool:
+            rows = pool.map(_long_rows, cases, chunksize=1)
+    else:
+        rows = [_long_rows(c) for c in cases]
+    with open(out, "wb") as raw, gzip.GzipFile(fileobj=raw, mode="wb", filename="", mtime=0) as f:
+        for case, r in zip(cases, rows):
+            case["rows"] = r
+            f.write((json.dumps(case, separators=(",", ":")) + "\n").encode())
+    print(f"wrote {len(cases)} cases to {out} ({os.path.getsize(out)} bytes)")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reference", required=True, help="checkout of the reference repository (holds utils/repeat_tracker.py)")
     ap.add_argument("--cases", type=int, default=3200)
-    ap.add_argument("--seed", type=int, default=9)
-    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--seed", type=int, default=None, help="default: 9, with --long 17")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--long", action="store_true", help="write the long fixture (interrupted_long.jsonl.gz) instead")
+    ap.add_argument("--jobs", type=int, default=4, help="--long: processes that run the reference")
     args = ap.parse_args()
     sys.dont_write_bytecode = True
     sys.path.insert(0, os.path.abspath(args.reference))
     from utils.repeat_tracker import RepeatTracker
+    if args.long:
+        write_long(RepeatTracker, 17 if args.seed is None else args.seed, args.out or LONG_OUT, args.jobs)
+        return
+    args.seed = 9 if args.seed is None else args.seed
+    args.out = args.out or OUT
     rng = random.Random(args.seed)
     with gzip.open(args.out, "wt") as f:
         for i in range(args.cases):
