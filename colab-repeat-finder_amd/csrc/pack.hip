@@ -1,10 +1,11 @@
-// pack.hip -- ASCII -> bit planes, on the device.
+// pack.hip -- ASCII -> bit planes (linear and bit-sliced), on the device.
 //
 // Replaces the reference's input_sequence.upper() plus its two further whole-sequence copies
 // (reference perfect_repeat_finder.py:33, :46): the ASCII bytes are read once, case-folded in
 // registers and written as three 1-bit planes (H, L = base code, X = not-ACGT).
 #include "prf_device.h"
 #include "prf_host.h"
+#include "scan_vertical.h"
 
 // One thread packs one 64-position word: 64 bytes in (4 x 16-B loads), 3 x 8 bytes out.
 // Symbols: A, C, G, T -> code; N -> X; any other LETTER is an ordinary symbol to the reference (R == R matches,
@@ -217,4 +218,111 @@ hipError_t prf_launch_fill_u64(hipStream_t s, u64 *p, u64 n, u64 v) {
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(prf_fill_u64_kernel, dim3((u32)nb), dim3(256), 0, s, p, n, v);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The bit-sliced ("vertical") planes of the fused scan kernel (layout: scan_vertical.hip), their tile classes and launch list.
+namespace {
+
+using prf_layout::T; using prf_layout::RG;  // (prf_plan.h)
+
+// ASCII -> bit-sliced planes.  One wave per tile; lane l, for bit b = 0..31, reads the 32 consecutive
+// bytes of stream b*64+l (a wave reads 2 KiB contiguous per b) and spreads them over its 32 row words.
+__global__ __launch_bounds__(64) void prf_pack_vertical_kernel(const uint8_t *__restrict__ asc, u32 *__restrict__ VH,
+                                                               u32 *__restrict__ VL,
+                                                               unsigned char *__restrict__ any_all) {
+    const u64 tile = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    u32 h[T], l[T], x[T];
+    u32 exo = 0;  // any letter other than A, C, G, T, N
+#pragma unroll
+    for (int t = 0; t < T; t++) h[t] = l[t] = x[t] = 0;
+    const uint8_t *base = asc + tile * PRF_TILE + (u64)lane * T;
+    for (int b = 0; b < 32; b++) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(base + (u64)b * (64 * T));
+        const uint4 v0 = src[0], v1 = src[1];
+        const u32 d[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+        for (int t = 0; t < T; t++) {
+            const u32 f = (d[t >> 2] >> (8 * (t & 3))) & 0xDFu;
+            const u32 ok = (f == 'A') | (f == 'C') | (f == 'G') | (f == 'T');
+            h[t] |= ((f >> 2) & 1u & ok) << b;
+            l[t] |= ((f >> 1) & 1u & ok) << b;
+            x[t] |= (ok ^ 1u) << b;
+            exo |= (ok | (f == 'N')) ^ 1u;
+        }
+    }
+    u32 any = 0, all = ~0u;
+#pragma unroll
+    for (int t = 0; t < T; t++) {
+        any |= x[t];
+        all &= x[t];
+    }
+    uint4 *oh = reinterpret_cast<uint4 *>(VH) + tile * RG * 64 + lane;
+    uint4 *ol = reinterpret_cast<uint4 *>(VL) + tile * RG * 64 + lane;
+#pragma unroll
+    for (int rg = 0; rg < RG; rg++) {
+        oh[rg * 64] = make_uint4(h[4 * rg], h[4 * rg + 1], h[4 * rg + 2], h[4 * rg + 3]);
+        ol[rg * 64] = make_uint4(l[4 * rg], l[4 * rg + 1], l[4 * rg + 2], l[4 * rg + 3]);
+    }
+    const bool w_any = __builtin_amdgcn_ballot_w64(any != 0) != 0;
+    const bool w_all = __builtin_amdgcn_ballot_w64(all != ~0u) == 0;
+    const bool w_exo = __builtin_amdgcn_ballot_w64(exo != 0) != 0;
+    if (lane == 0) any_all[tile] = (unsigned char)((w_any ? 1 : 0) | (w_all ? 2 : 0) | (w_exo ? 4 : 0));
+}
+
+// class: 3 = a symbol outside ACGTN in this tile, the one before or the one after (such tiles are scanned by the generic
+// kernels, with the symbols' own planes); 2 = only not-ACGT; 1 = some not-ACGT in this tile or the next (whose first lanes
+// are this tile's virtual lanes 64..); 0 = clean
+__global__ void prf_tile_class_kernel(const unsigned char *__restrict__ any_all, unsigned char *__restrict__ cls, u64 ntiles) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ntiles) return;
+    const unsigned char a = any_all[i];
+    const unsigned char b = (i + 1 < ntiles) ? any_all[i + 1] : (unsigned char)3;
+    const unsigned char p = i ? any_all[i - 1] : (unsigned char)0;
+    cls[i] = ((a | b | p) & 4) ? 3 : ((a & 2) ? 2 : (((a | b) & 1) ? 1 : 0));
+}
+
+}  // namespace
+
+// first tile if the list is one contiguous range of clean tiles, else ~0u
+u32 prf_flat_base(const u32 *list, size_t n) {
+    if (n == 0 || (list[0] & PRF_LAUNCH_MIXED)) return ~0u;
+    for (size_t i = 1; i < n; i++)
+        if (list[i] != list[0] + (u32)i) return ~0u;
+    return list[0];
+}
+
+int prf_vertical_pack(hipStream_t s, const uint8_t *asc, u64 G, prf_vplanes *vp) {
+    const u64 ntiles = G / PRF_TILE;  // includes the sentinel tile
+    hipError_t e;
+    const size_t plane_bytes = (size_t)ntiles * RG * 64 * sizeof(uint4);
+    if ((e = hipMalloc((void **)&vp->VH, plane_bytes)) != hipSuccess) return (int)e;
+    if ((e = hipMalloc((void **)&vp->VL, plane_bytes)) != hipSuccess) return (int)e;
+    if ((e = hipMalloc((void **)&vp->tile_class, 2 * ntiles)) != hipSuccess) return (int)e;
+    if ((e = hipMalloc((void **)&vp->launch_list, sizeof(u32) * ntiles)) != hipSuccess) return (int)e;
+    vp->ntiles_alloc = ntiles;
+    unsigned char *any_all = vp->tile_class + ntiles;
+    hipLaunchKernelGGL(prf_pack_vertical_kernel, dim3((u32)ntiles), dim3(64), 0, s, asc, vp->VH, vp->VL, any_all);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(prf_tile_class_kernel, dim3((u32)((ntiles + 255) / 256)), dim3(256), 0, s, any_all, vp->tile_class, ntiles);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    // launch list (host side: one byte per 65536 positions)
+    vp->h_class.resize(ntiles);
+    if ((e = hipMemcpyAsync(vp->h_class.data(), vp->tile_class, ntiles, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+    vp->h_list.clear();
+    vp->h_list.reserve(ntiles);
+    for (u64 t = 0; t + 1 < ntiles; t++) {  // the sentinel tile is never scanned
+        if (vp->h_class[t] == 0) vp->h_list.push_back((u32)t);
+        else if (vp->h_class[t] == 1) vp->h_list.push_back((u32)t | PRF_LAUNCH_MIXED);
+    }
+    vp->n_launch = (u32)vp->h_list.size();
+    vp->flat_base = prf_flat_base(vp->h_list.data(), vp->h_list.size());
+    if (!vp->h_list.empty()) {
+        if ((e = hipMemcpyAsync(vp->launch_list, vp->h_list.data(), sizeof(u32) * vp->h_list.size(), hipMemcpyHostToDevice, s)) != hipSuccess)
+            return (int)e;
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+    }
+    return 0;
 }

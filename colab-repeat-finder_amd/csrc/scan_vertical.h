@@ -1,4 +1,4 @@
-// scan_vertical.h -- host interface of the fused bit-sliced ("vertical") scan kernel and its row gather.
+// scan_vertical.h -- host interface of the fused bit-sliced ("vertical") scan kernel, its row gather and its packer.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -76,11 +76,15 @@ struct prf_vgather_args {
 };
 
 
+// ---- scan_vertical.hip: the fused scan kernel ----
+hipError_t prf_vertical_launch(hipStream_t s, const prf_vscan_args &args);
+
+// ---- scan_gather.hip: the row gather ----
+hipError_t prf_vertical_gather(hipStream_t s, const prf_vgather_args &args);
+
+// ---- pack.hip: the bit-sliced planes ----
 // ASCII (global coordinate space, G bytes) -> bit-sliced planes + tile classes + launch list. Synchronises the stream.
 int prf_vertical_pack(hipStream_t s, const uint8_t *asc, u64 G, prf_vplanes *vp);
 
 // first tile if the list is one contiguous range of clean tiles, else ~0u
 u32 prf_flat_base(const u32 *list, size_t n);
-
-hipError_t prf_vertical_launch(hipStream_t s, const prf_vscan_args &args);
-hipError_t prf_vertical_gather(hipStream_t s, const prf_vgather_args &args);
