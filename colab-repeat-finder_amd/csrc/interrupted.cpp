@@ -1,5 +1,7 @@
 // interrupted.cpp -- the host path of the interrupted repeats (prf_scan_interrupted*; kernels: scan_interrupted.hip).
 //
+// Every entry point is prf_scan_interrupted_by_k: a budget of varying phases per motif size.  The older ones hand
+// it the same budget for every motif size and keep their refusal of 0.
 // Whole sequences, one call, in stages that each hand a named struct to the next (interrupted_scan runs them):
 //   check_args       the refusals, parameters first
 //   stage_sequences  placement, upload, upper-casing (+ the first byte that is not a letter), N-trimming -> first_last
@@ -22,12 +24,18 @@
 namespace {
 
 struct int_params {
-    u32 kmin, kmax, min_repeats, min_span, max_int, memo_stride;
+    u32 kmin, kmax, min_repeats, min_span, memo_stride;
     u64 memo_slots;
     // 0: one lane per (sequence, k), one lane per thread (prf_scan_interrupted_ex).  Otherwise the landings of each (sequence, k)
     // are cut into chunks of `chunk` positions, one lane per wave.
     u64 chunk;
+    // the budget of varying phases per motif size: by_k[j] for k = kmin + j (the caller's array, read during the call only), or
+    // `uniform` for every k where an older entry point gave one number (by_k == NULL, uniform_call)
+    const u32 *by_k;
+    u32 uniform;
+    bool uniform_call;
     u32 nk() const { return kmax - kmin + 1; }
+    u32 max_int(u32 j) const { return uniform_call ? uniform : by_k[j]; }
 };
 
 // the timing events of one call, each recorded once
@@ -102,9 +110,10 @@ int to_host(hipStream_t st, const T *d, std::vector<T> *h) {
 int interrupted_check(const int_params &p) {
     int rc = check_params(p.kmin, p.kmax, p.min_repeats, p.min_span, 0);
     if (rc) return rc;
-    if (p.max_int < 1)
+    if (p.uniform_call && p.uniform < 1)
         return fail(PRF_EINVAL, "max_interruptions is %u: prf_scan_interrupted serves max_interruptions >= 1 (0 is prf_scan's perfect path)",
-                    p.max_int);
+                    p.uniform);
+    if (!p.uniform_call && !p.by_k) return fail(PRF_EINVAL, "prf_scan_interrupted_by_k: NULL max_interruptions_by_k");
     if (p.min_repeats < 2)
         return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: min_repeats == 1 is not supported with interruptions (min_repeats >= 2)");
     if (p.kmax > 64) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: max_motif_size %u > 64 (the phase set is one 64-bit mask)", p.kmax);
@@ -197,6 +206,7 @@ int lay_out_lanes(const std::vector<u64> &base, const std::vector<u64> &len, con
                 ln.seq_base = base[i];
                 ln.chunk = ch;
                 ln.kslot = i * nk + j;
+                ln.max_int = p.max_int(j);
                 ln.lo = (u64)ch * p.chunk;
                 ln.hi = p.chunk ? (u64)(ch + 1) * p.chunk : (u64)INT64_MAX;
                 ln.memo_slots = p.memo_stride ? std::min<u64>(p.memo_slots, reach / p.memo_stride + 1) : 0;
@@ -268,7 +278,7 @@ int walk(prf_ctx *c, const int_events &ev, const staged_seqs &s, const int_param
         prf_int_walk_args a{};
         a.l = w->dev;
         a.buf = s.d_buf.p;
-        a.min_repeats = p.min_repeats; a.min_span = p.min_span; a.max_int = p.max_int; a.stride = p.memo_stride;
+        a.min_repeats = p.min_repeats; a.min_span = p.min_span; a.stride = p.memo_stride;
         a.first_end = p.chunk ? w->d_first_end.p : nullptr;
         a.memo = w->d_memo.p;
         a.eps = room->d_eps.p;
@@ -425,7 +435,7 @@ int prf_scan_interrupted_ex(prf_ctx *c, const prf_contig *contigs, int n_contigs
                             uint32_t min_span, uint32_t max_interruptions, uint32_t memo_stride, uint64_t memo_slots, prf_ihits *out,
                             prf_scan_stats *stats, uint64_t *counters) {
     return guarded("prf_scan_interrupted", [&] {
-        const int_params p{kmin, kmax, min_repeats, min_span, max_interruptions, memo_stride, memo_slots, 0};
+        const int_params p{kmin, kmax, min_repeats, min_span, memo_stride, memo_slots, 0, nullptr, max_interruptions, true};
         return interrupted_scan(c, contigs, n_contigs, p, out, stats, counters, 4);
     });
 }
@@ -434,7 +444,16 @@ int prf_scan_interrupted_chunked(prf_ctx *c, const prf_contig *contigs, int n_co
                                  uint32_t min_span, uint32_t max_interruptions, uint32_t memo_stride, uint64_t memo_slots, uint64_t chunk,
                                  prf_ihits *out, prf_scan_stats *stats, uint64_t *counters) {
     return guarded("prf_scan_interrupted_chunked", [&] {
-        const int_params p{kmin, kmax, min_repeats, min_span, max_interruptions, memo_stride, memo_slots, chunk};
+        const int_params p{kmin, kmax, min_repeats, min_span, memo_stride, memo_slots, chunk, nullptr, max_interruptions, true};
+        return interrupted_scan(c, contigs, n_contigs, p, out, stats, counters, 6);
+    });
+}
+
+int prf_scan_interrupted_by_k(prf_ctx *c, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax, uint32_t min_repeats,
+                              uint32_t min_span, const uint32_t *max_interruptions_by_k, uint32_t memo_stride, uint64_t memo_slots,
+                              uint64_t chunk, prf_ihits *out, prf_scan_stats *stats, uint64_t *counters) {
+    return guarded("prf_scan_interrupted_by_k", [&] {
+        const int_params p{kmin, kmax, min_repeats, min_span, memo_stride, memo_slots, chunk, max_interruptions_by_k, 0, false};
         return interrupted_scan(c, contigs, n_contigs, p, out, stats, counters, 6);
     });
 }

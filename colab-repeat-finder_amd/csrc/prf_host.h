@@ -70,6 +70,7 @@ struct prf_ilane {
     u32 seq, k;
     u64 lo, hi;               // the lane walks the episodes that land in [lo, hi) (trimmed positions); lo == 0: from position 0
     u32 chunk, kslot;         // its chunk's number within (sequence, k); index of that (sequence, k)
+    u32 max_int, pad_;        // phases of the motif that may vary in this lane: the budget of its motif size (0: none)
 };
 struct prf_icand {            // an output check that passed both span tests with no N in the motif
     u64 start, end, mask;     // trimmed coordinates; mask: the phases allowed to vary
@@ -101,7 +102,7 @@ struct prf_int_lanes {
 struct prf_int_walk_args {
     prf_int_lanes l;
     const uint8_t *buf;
-    u32 min_repeats, min_span, max_int, stride;
+    u32 min_repeats, min_span, stride;  // (the budget of varying phases travels with each lane)
     u32 *first_end;
     prf_imemo *memo;
     u32 *eps;

@@ -50,12 +50,14 @@ __host__ __device__ __forceinline__ u64 memo_slot(u64 pos, u64 run, u64 mask, u6
 // One lane: the walk of (sequence, k) restricted to the landings in [ln.lo, ln.hi).  lane_end[li] = 1 if the walk ended in one
 // of this lane's episodes (at the end of the sequence).  first_end (may be NULL): per (sequence, k) the smallest chunk whose lane
 // ended; a lane behind that chunk is dropped by the host and stops when it sees so (polled every 64 positions).
-// SKIP_ABSORBED: a run whose phase set holds all k phases (k <= max_int) absorbs every mismatch, so it only ends with the sequence:
+// The budget of varying phases is the lane's own (prf_ilane::max_int); 0: no phase is ever added, the first
+// interruption is still recorded and the reset still jumps to it.
+// SKIP_ABSORBED: a run whose phase set holds all k phases (k <= the lane's max_int) absorbs every mismatch, so it only ends with the sequence:
 // the lane moves to n - k at once, counting the moves it did not make (the memo records of that stretch are not written, so the
 // lookup and hit counters differ from a walk that makes them; the one-lane engine keeps making them).
 template <bool SKIP_ABSORBED>
 __device__ __forceinline__ void walk_lane(const uint8_t *__restrict__ buf, const prf_ilane *__restrict__ lanes, u32 li,
-                                          const u64 *__restrict__ first_last, u32 min_repeats, u32 min_span, u32 max_int, u32 stride,
+                                          const u64 *__restrict__ first_last, u32 min_repeats, u32 min_span, u32 stride,
                                           prf_icand *__restrict__ cands, u64 *__restrict__ cand_cnt, u32 *__restrict__ lane_end,
                                           u32 *__restrict__ first_end, prf_imemo *__restrict__ memo, u32 *__restrict__ eps,
                                           u64 *__restrict__ counters) {
@@ -65,6 +67,7 @@ __device__ __forceinline__ void walk_lane(const uint8_t *__restrict__ buf, const
     const i64 n = f0 == ~0ull ? 0 : (i64)(f1 - f0);
     const uint8_t *__restrict__ base = buf + ln.seq_base;  // 16-byte aligned; position p of the trimmed sequence is base[head + p]
     const i64 k = ln.k;
+    const u32 max_int = ln.max_int;
     const i64 span = min_span, r_span = (i64)min_repeats * k;
     prf_icand *__restrict__ my_cands = cands + ln.cand_off;
     prf_imemo *__restrict__ my_memo = memo + ln.memo_off;
@@ -240,13 +243,13 @@ __device__ __forceinline__ void walk_lane(const uint8_t *__restrict__ buf, const
 
 __global__ void __launch_bounds__(64) prf_int_walk_kernel(const uint8_t *__restrict__ buf, const prf_ilane *__restrict__ lanes,
                                                           u32 n_lanes, const u64 *__restrict__ first_last, u32 min_repeats,
-                                                          u32 min_span, u32 max_int, u32 stride, prf_icand *__restrict__ cands,
+                                                          u32 min_span, u32 stride, prf_icand *__restrict__ cands,
                                                           u64 *__restrict__ cand_cnt, u32 *__restrict__ lane_end,
                                                           prf_imemo *__restrict__ memo, u32 *__restrict__ eps,
                                                           u64 *__restrict__ counters) {
     const u32 li = blockIdx.x * blockDim.x + threadIdx.x;
     if (li >= n_lanes) return;
-    walk_lane<false>(buf, lanes, li, first_last, min_repeats, min_span, max_int, stride, cands, cand_cnt, lane_end, nullptr, memo, eps, counters);
+    walk_lane<false>(buf, lanes, li, first_last, min_repeats, min_span, stride, cands, cand_cnt, lane_end, nullptr, memo, eps, counters);
 }
 
 // One lane per wave (the first thread of each 64-thread workgroup): a lane is a chain of dependent loads, and lanes that share a
@@ -254,13 +257,13 @@ __global__ void __launch_bounds__(64) prf_int_walk_kernel(const uint8_t *__restr
 // number of waves in flight, so the other 63 threads stay idle.
 __global__ void __launch_bounds__(64) prf_int_walk_chunk_kernel(const uint8_t *__restrict__ buf, const prf_ilane *__restrict__ lanes,
                                                                 u32 n_lanes, const u64 *__restrict__ first_last, u32 min_repeats,
-                                                                u32 min_span, u32 max_int, u32 stride, prf_icand *__restrict__ cands,
+                                                                u32 min_span, u32 stride, prf_icand *__restrict__ cands,
                                                                 u64 *__restrict__ cand_cnt, u32 *__restrict__ lane_end,
                                                                 u32 *__restrict__ first_end, prf_imemo *__restrict__ memo,
                                                                 u32 *__restrict__ eps, u64 *__restrict__ counters) {
     const u32 li = blockIdx.x;
     if (li >= n_lanes || threadIdx.x != 0) return;
-    walk_lane<true>(buf, lanes, li, first_last, min_repeats, min_span, max_int, stride, cands, cand_cnt, lane_end, first_end, memo, eps, counters);
+    walk_lane<true>(buf, lanes, li, first_last, min_repeats, min_span, stride, cands, cand_cnt, lane_end, first_end, memo, eps, counters);
 }
 
 // boundaries of each lane's chunk (an upper bound of its episodes, hence of its candidates): one workgroup per lane
@@ -405,11 +408,11 @@ hipError_t prf_launch_int_walk(hipStream_t st, const prf_int_walk_args &a) {
     if (!l.n_lanes) return hipSuccess;
     if (a.first_end)
         hipLaunchKernelGGL(prf_int_walk_chunk_kernel, dim3(l.n_lanes), dim3(64), 0, st, a.buf, l.lanes, l.n_lanes, l.first_last,
-                           a.min_repeats, a.min_span, a.max_int, a.stride, l.cands, l.cand_cnt, l.lane_end, a.first_end, a.memo, a.eps,
+                           a.min_repeats, a.min_span, a.stride, l.cands, l.cand_cnt, l.lane_end, a.first_end, a.memo, a.eps,
                            a.counters);
     else
         hipLaunchKernelGGL(prf_int_walk_kernel, dim3((l.n_lanes + 63) / 64), dim3(64), 0, st, a.buf, l.lanes, l.n_lanes, l.first_last,
-                           a.min_repeats, a.min_span, a.max_int, a.stride, l.cands, l.cand_cnt, l.lane_end, a.memo, a.eps, a.counters);
+                           a.min_repeats, a.min_span, a.stride, l.cands, l.cand_cnt, l.lane_end, a.memo, a.eps, a.counters);
     return hipGetLastError();
 }
 

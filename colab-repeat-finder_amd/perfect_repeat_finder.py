@@ -108,15 +108,54 @@ def _masked_motif(seq, start, k, nmask):
     return motif
 
 
-def _interrupted_rows(seqs, fs, context=None):
+def parse_interruption_spec(spec, min_motif_size, max_motif_size):
+    """--max-interruptions-by-motif-size: "1-2:0,3-6:1,7-:2" -> {k: m}.  Items are K:M, A-B:M or A-:M (up to max_motif_size),
+    comma-separated.  ValueError for a malformed item, ranges that overlap, or a motif size outside min .. max."""
+    out = {}
+    for item in spec.split(","):
+        m = re.fullmatch(r"\s*(\d+)(?:(-)(\d*))?:(\d+)\s*", item)
+        if not m:
+            raise ValueError(f"malformed item {item!r}: expected K:M, A-B:M or A-:M")
+        first = int(m.group(1))
+        last = first if not m.group(2) else max_motif_size if m.group(3) == "" else int(m.group(3))
+        if last < first:
+            raise ValueError(f"malformed item {item!r}: the range {first}-{last} is empty")
+        if first < min_motif_size or last > max_motif_size:
+            raise ValueError(f"item {item!r} names motif sizes outside {min_motif_size} .. {max_motif_size}")
+        for k in range(first, last + 1):
+            if k in out:
+                raise ValueError(f"item {item!r} overlaps an earlier one at motif size {k}")
+            out[k] = int(m.group(4))
+    return out
+
+
+def _interruption_budgets(fs):
+    """(max_interruptions, budgets): budgets is None where fs has no max_interruptions_by_motif_size, else the budget of every
+    motif size min .. max as a list -- the dict's value, or max_interruptions for a k it omits (keys outside the range are
+    ignored: the reference's tests pass a dict for 1 .. 49 whatever the range)."""
+    max_int = getattr(fs, "max_interruptions", 0) or 0
+    if max_int < 0:
+        raise ValueError(f"max_interruptions is set to {max_int}. It must be at least 0.")
+    by_size = getattr(fs, "max_interruptions_by_motif_size", None)
+    if by_size is None:
+        return max_int, None
+    if not isinstance(by_size, dict):
+        raise ValueError("max_interruptions_by_motif_size must be a dict {motif size: max interruptions}")
+    return max_int, prf_native.interruption_budgets(fs.min_motif_size, fs.max_motif_size, max_int, by_size, ignore_other_k=True)
+
+
+def _interrupted_rows(seqs, fs, context=None, budgets=None):
     """Interrupted repeats of whole sequences, all in one call (csrc/scan_interrupted.hip): numpy rows (start, end, k, contig,
     nmask) sorted by (contig, start, end).  The walk runs in chunks of fs.interrupted_chunk landing positions (default: the
-    library's PRF_INT_CHUNK; 0: one lane per motif size); the rows do not depend on it."""
+    library's PRF_INT_CHUNK; 0: one lane per motif size); the rows do not depend on it.  budgets: one per motif size
+    (_interruption_budgets), None: fs.max_interruptions for all."""
     ctx = context or prf_native.default_context()
     chunk = getattr(fs, "interrupted_chunk", None)
     try:
         rows, _stats = ctx.scan_interrupted(seqs, fs.min_motif_size, fs.max_motif_size, fs.min_repeats, fs.min_span,
-                                            fs.max_interruptions, chunk=prf_native.INT_CHUNK if chunk is None else chunk)
+                                            0 if budgets is not None else fs.max_interruptions,
+                                            chunk=prf_native.INT_CHUNK if chunk is None else chunk,
+                                            **({} if budgets is None else {"max_interruptions_by_k": budgets}))
     except prf_native.PrfError as exc:
         if exc.code in (prf_native.PRF_EINVAL, prf_native.PRF_ESYMBOL, prf_native.PRF_EUNSUPPORTED):
             raise ValueError(exc.message) from None
@@ -128,17 +167,23 @@ def detect_repeats(input_sequence, filter_settings, verbose=False, show_progress
     """Detect perfect tandem repeats; see the module docstring.  `context` (a prf_native.Context) is an
     extension: by default a process-wide context on device PRF_DEVICE / LOCAL_RANK / 0 is used.
     filter_settings.max_interruptions > 0 (an extension, the reference's RepeatTracker): interrupted repeats of the whole
-    sequence by the driver of DESIGN 9; the motif has N at the phases allowed to vary."""
+    sequence by the driver of DESIGN 9; the motif has N at the phases allowed to vary.
+    filter_settings.max_interruptions_by_motif_size, a dict {k: m}: motif size k gets RepeatTracker(k, ..., m), a k
+    the dict omits gets max_interruptions (default 0), all over one dictionary of rows.  If no motif size of the range ends up
+    with a budget above 0 this is the perfect scan, exactly as without the dict.  Otherwise a motif size with budget 0 is scanned
+    by RepeatTracker with max_interruptions = 0 like the others, not by PerfectRepeatTracker: the two differ in the homopolymer
+    rule (RepeatTracker reports no motif of k > 1 that is one repeated base) and in the previous-output rule (it drops a row that
+    ends less than k behind the one before it).  A negative value raises ValueError."""
     _check_settings(filter_settings)
     fs = filter_settings
-    max_int = getattr(fs, "max_interruptions", 0) or 0
-    if max_int < 0:
-        raise ValueError(f"max_interruptions is set to {max_int}. It must be at least 0.")
-    if max_int > 0:
+    max_int, budgets = _interruption_budgets(fs)
+    if budgets is not None and not any(budgets):
+        max_int, budgets = 0, None      # nothing may vary anywhere: the perfect path
+    if max_int > 0 or budgets is not None:
         if hasattr(fs, "interval_start_0based") or hasattr(fs, "interval_end"):
             raise ValueError("interval mode is not supported with max_interruptions > 0: the lock-step loop's stopping rule is "
                              "undefined for a tracker that jumps back; scan the whole sequence")
-        rows = _interrupted_rows([_to_ascii(input_sequence)], fs, context)
+        rows = _interrupted_rows([_to_ascii(input_sequence)], fs, context, budgets=budgets)
         return [(int(r["start"]), int(r["end"]), _masked_motif(input_sequence, int(r["start"]), int(r["k"]), int(r["nmask"])))
                 for r in rows]
     has_interval = hasattr(fs, "interval_start_0based") or hasattr(fs, "interval_end")
@@ -202,6 +247,10 @@ def _build_parser():
     g.add_argument("--max-interruptions", type=int, default=0,
                    help="(the reference's RepeatTracker) how many positions within the motif may vary across repeats; 0: perfect "
                         "repeats only.  Whole sequences only (no --interval), min repeats >= 2, max motif size <= 64.")
+    g.add_argument("--max-interruptions-by-motif-size", default=None, metavar="SPEC",
+                   help="--max-interruptions per motif size, as comma-separated ranges: 1-2:0,3-6:1,7-:2 (K:M for one size; A-: up "
+                        "to --max-motif-size).  A size that SPEC leaves out takes --max-interruptions.  If no size ends up above 0 "
+                        "the perfect scan runs.  Otherwise a size with 0 is scanned by the same tracker without varying positions.")
     g.add_argument("--interrupted-chunk", type=int, default=None, metavar="N",
                    help="With --max-interruptions > 0: positions of a sequence that one GPU lane walks (default: the library's, "
                         "2^20; 0: one lane per motif size).  The output does not depend on it.")
@@ -390,7 +439,7 @@ def _scan_fasta_interrupted(args, bed_path):
     fasta = prf_native.Fasta(args.input_sequence)     # holds the records' native memory until the rows are written
     entries = list(fasta)
     _check_settings(args)
-    rows = _interrupted_rows([(e.addr, e.length) for e in entries], args)
+    rows = _interrupted_rows([(e.addr, e.length) for e in entries], args, budgets=_interruption_budgets(args)[1])
     import numpy as np
     counts = np.bincount(rows["contig"], minlength=len(entries)) if len(rows) else np.zeros(len(entries), dtype=np.int64)
     with open(bed_path, "wt") as bed:
@@ -411,7 +460,8 @@ def _scan_fasta(args, parser):
     if not args.output_prefix:
         args.output_prefix = re.sub(".fa(sta)?(.gz)?", "", args.input_sequence)   # same unanchored pattern as reference :114
     bed_path = f"{os.path.basename(args.output_prefix)}.bed"
-    if args.max_interruptions > 0:
+    budgets = _interruption_budgets(args)[1]
+    if (args.max_interruptions > 0 and budgets is None) or (budgets is not None and any(budgets)):
         if args.interval:
             parser.error("--interval is not supported with --max-interruptions > 0 (the lock-step loop's stopping rule is undefined "
                          "for a tracker that jumps back): scan whole records")
@@ -494,6 +544,12 @@ def main(argv=None):
         parser.error(f"--min-span is set to {args.min_span}. It must be at least 1.")
     if args.max_interruptions < 0:
         parser.error(f"--max-interruptions is set to {args.max_interruptions}. It must be at least 0.")
+    if args.max_interruptions_by_motif_size is not None:
+        try:
+            args.max_interruptions_by_motif_size = parse_interruption_spec(args.max_interruptions_by_motif_size, args.min_motif_size,
+                                                                           args.max_motif_size)
+        except ValueError as exc:
+            parser.error(f"--max-interruptions-by-motif-size: {exc}")
     if args.interrupted_chunk is not None and (args.interrupted_chunk < 0 or 0 < args.interrupted_chunk < prf_native.INT_CHUNK_MIN):
         parser.error(f"--interrupted-chunk is set to {args.interrupted_chunk}. It must be 0 or at least {prf_native.INT_CHUNK_MIN}.")
     if os.path.isfile(args.input_sequence):

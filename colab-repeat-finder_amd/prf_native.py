@@ -5,6 +5,7 @@ device is usable, the calls raise.  PyTorch is not involved; the library owns it
 memory and its HIP stream.
 """
 import ctypes
+import operator
 import os
 import threading
 
@@ -76,6 +77,35 @@ class ScanStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+def interruption_budgets(kmin, kmax, max_interruptions, by_k, ignore_other_k=False):
+    """The budget of varying phases of every motif size kmin .. kmax as a list (entry j: k = kmin + j).  by_k: a dict {k: m} --
+    a k it omits takes max_interruptions; a key outside kmin .. kmax is a ValueError unless ignore_other_k -- or a sequence with
+    one entry per motif size; a sequence names every k, so a max_interruptions other than 0 that disagrees with one of its
+    entries is a ValueError.  A negative or non-integer budget is a ValueError."""
+    if kmin < 1 or kmax < kmin:
+        raise ValueError(f"motif sizes {kmin} .. {kmax}: an empty range")
+    scalar = max_interruptions or 0
+    if isinstance(by_k, dict):
+        other = sorted(k for k in by_k if not (isinstance(k, int) and kmin <= k <= kmax))
+        if other and not ignore_other_k:
+            raise ValueError(f"max_interruptions_by_k names motif size {other[0]}, outside {kmin} .. {kmax}")
+        out = [by_k.get(k, scalar) for k in range(kmin, kmax + 1)]
+    else:
+        out = list(by_k)
+        if len(out) != kmax - kmin + 1:
+            raise ValueError(f"max_interruptions_by_k has {len(out)} entries for the {kmax - kmin + 1} motif sizes {kmin} .. {kmax}")
+        if scalar and any(m != scalar for m in out):
+            raise ValueError(f"max_interruptions is {scalar} and max_interruptions_by_k gives another budget: pass one of them, or 0")
+    for j, m in enumerate(out):
+        try:
+            out[j] = operator.index(m)
+        except TypeError:
+            out[j] = -1
+        if isinstance(m, bool) or not 0 <= out[j] <= 0xFFFFFFFF:
+            raise ValueError(f"max_interruptions for motif size {kmin + j} is set to {m}. It must be at least 0.")
+    return out
+
+
 EXPORTS = ["prf_abi_version", "prf_device_count", "prf_last_error", "prf_open", "prf_close", "prf_genome_load",
            "prf_genome_free", "prf_genome_positions", "prf_scan_genome", "prf_scan", "prf_free_hits",
            "prf_measure_hbm_read", "prf_last_hits_to_device", "prf_plan_describe", "prf_fasta_open", "prf_fasta_count",
@@ -83,7 +113,7 @@ EXPORTS = ["prf_abi_version", "prf_device_count", "prf_last_error", "prf_open", 
            "prf_scan_wait", "prf_genome_standin", "prf_genome_select", "prf_genome_tile_classes", "prf_tile_positions", "prf_scan_timings_split", "prf_last_hits_packed_to_device",
            "prf_genome_contig_bases", "prf_scan_literal", "prf_scan_genome_async_packed", "prf_stream_wait_for",
            "prf_genome_footprint", "prf_scan_interrupted", "prf_scan_interrupted_ex", "prf_free_ihits",
-           "prf_scan_interrupted_chunked"]
+           "prf_scan_interrupted_chunked", "prf_scan_interrupted_by_k"]
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -157,6 +187,9 @@ def load_library():
             ctypes.c_uint64, ctypes.POINTER(_IHits), ctypes.POINTER(ScanStats), ctypes.POINTER(ctypes.c_uint64)]
         lib.prf_scan_interrupted_chunked.argtypes = [vp, ctypes.POINTER(_Contig), ctypes.c_int] + [ctypes.c_uint32] * 6 + [
             ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(_IHits), ctypes.POINTER(ScanStats), ctypes.POINTER(ctypes.c_uint64)]
+        lib.prf_scan_interrupted_by_k.argtypes = [vp, ctypes.POINTER(_Contig), ctypes.c_int] + [ctypes.c_uint32] * 4 + [
+            ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(_IHits),
+            ctypes.POINTER(ScanStats), ctypes.POINTER(ctypes.c_uint64)]
         lib.prf_free_ihits.argtypes = [ctypes.POINTER(_IHits)]
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
@@ -359,21 +392,27 @@ class Context:
             self.lib.prf_free_hits(ctypes.byref(hits))
 
     def scan_interrupted(self, seqs, kmin, kmax, min_repeats, min_span, max_interruptions, memo_stride=None, memo_slots=None,
-                         counters=False, chunk=None):
+                         counters=False, chunk=None, max_interruptions_by_k=None):
         """Interrupted repeats of many whole sequences in one call (prf_scan_interrupted): (rows, stats[, counters]).  rows: numpy
         records (start, end, k, contig, nmask) sorted by (contig, start, end); bit i of nmask = phase i of the motif may vary.
         memo_stride / memo_slots: the walk's memo table (the rows do not depend on it); counters: also return a dict of the
         walk's steps, memo lookups, memo hits and recorded episodes.  chunk: None = one lane per (sequence, motif size)
         (prf_scan_interrupted_ex); an integer = prf_scan_interrupted_chunked with that many landing positions per lane (0: one
         lane again; INT_CHUNK: the library's default), and the counters then also hold `lanes` and `dropped_lanes`.  The rows
-        do not depend on it."""
+        do not depend on it.  max_interruptions_by_k: a budget per motif size (prf_scan_interrupted_by_k), see
+        interruption_budgets(); every value >= 0 is served, all zeros included."""
         import numpy as np
         arr, _keep = _contig_array(list(seqs))
         hits, stats = _IHits(), ScanStats()
         ctr = (ctypes.c_uint64 * 6)()
         stride = MEMO_STRIDE if memo_stride is None else memo_stride
         slots = MEMO_SLOTS if memo_slots is None else memo_slots
-        if chunk is None:
+        if max_interruptions_by_k is not None:
+            by_k = interruption_budgets(kmin, kmax, max_interruptions, max_interruptions_by_k)
+            _check(self.lib, self.lib.prf_scan_interrupted_by_k(
+                self._h, arr, len(seqs), kmin, kmax, min_repeats, min_span, (ctypes.c_uint32 * len(by_k))(*by_k), stride, slots,
+                chunk or 0, ctypes.byref(hits), ctypes.byref(stats), ctr))
+        elif chunk is None:
             _check(self.lib, self.lib.prf_scan_interrupted_ex(
                 self._h, arr, len(seqs), kmin, kmax, min_repeats, min_span, max_interruptions, stride, slots,
                 ctypes.byref(hits), ctypes.byref(stats), ctr))

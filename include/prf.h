@@ -178,7 +178,9 @@ int prf_scan_literal(prf_ctx *ctx, const prf_contig *contig, uint32_t kmin, uint
  * is seq.upper()[start:start+k] with N at the phases set in nmask (the reference's final_motif).  Whole contigs, many per call;
  * min_repeats >= 2 and kmax <= 64 (PRF_EUNSUPPORTED otherwise), max_interruptions >= 1 (0 is prf_scan's perfect path:
  * PRF_EINVAL), PRF_ESYMBOL for a byte that is not a letter.  Rows sorted by (contig, start, end) on the device.
- * Stats: path = 3, phase1_ms = the walk kernel, phase2_ms = emission and sort. */
+ * Stats: path = 3, phase1_ms = the walk kernel, phase2_ms = emission and sort.
+ * prf_scan_interrupted_by_k gives every motif size a budget of its own, RepeatTracker(k, ..., m_k, ...), with the same driver and
+ * the same ONE dictionary; the three calls with one max_interruptions are that call with the same budget for every motif size. */
 typedef struct prf_ihit {
     uint64_t start;  /* 0-based, contig-local      */
     uint64_t end;    /* exclusive                  */
@@ -216,6 +218,15 @@ int prf_scan_interrupted_ex(prf_ctx *ctx, const prf_contig *contigs, int n_conti
 int prf_scan_interrupted_chunked(prf_ctx *ctx, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax,
                                  uint32_t min_repeats, uint32_t min_span, uint32_t max_interruptions, uint32_t memo_stride,
                                  uint64_t memo_slots, uint64_t chunk, prf_ihits *out, prf_scan_stats *stats, uint64_t *counters);
+/* prf_scan_interrupted_chunked with a budget per motif size: max_interruptions_by_k[j] is the max_interruptions of the tracker
+ * of k = kmin + j, kmax - kmin + 1 entries, read during the call only; NULL: PRF_EINVAL.  Every value is valid, 0 included: such
+ * a k is scanned by RepeatTracker with max_interruptions = 0 (no phase varies; it differs from prf_scan's PerfectRepeatTracker in
+ * the homopolymer rule and the previous-output rule), and all entries may be 0.  One call is not the merge of one call
+ * per budget: a row of a small k keeps the same (start, end) from a larger k.  The other refusals, the rows, the statistics and
+ * the six counters are those of prf_scan_interrupted_chunked. */
+int prf_scan_interrupted_by_k(prf_ctx *ctx, const prf_contig *contigs, int n_contigs, uint32_t kmin, uint32_t kmax,
+                              uint32_t min_repeats, uint32_t min_span, const uint32_t *max_interruptions_by_k, uint32_t memo_stride,
+                              uint64_t memo_slots, uint64_t chunk, prf_ihits *out, prf_scan_stats *stats, uint64_t *counters);
 void prf_free_ihits(prf_ihits *hits);
 
 /* Pipelined scans.  prf_scan_genome_async() enqueues a scan and returns its serial number at once;

@@ -8,6 +8,7 @@ ONE shared dict, `while t.advance(): pass; t.done()`, rows = sorted(out.items())
 
     python3 tools/gen_interrupted_golden.py --reference PATH_TO_REFERENCE_CHECKOUT [--cases 3200] [--seed 9]
     python3 tools/gen_interrupted_golden.py --reference PATH_TO_REFERENCE_CHECKOUT --long [--seed 17] [--jobs 4]
+    python3 tools/gen_interrupted_golden.py --reference PATH_TO_REFERENCE_CHECKOUT --by-k [--seed 31] [--jobs 4]
 
 --long writes tests/golden/interrupted_long.jsonl.gz instead: a few dozen cases of 3-40 kb (the short fixture stops at 600
 positions) in the same format and through the same driver, from one seed (long_cases() lists them): random ACGT of 5-40 kb with
@@ -17,6 +18,15 @@ and without planted interrupted repeats, 20 kb of two- and three-letter sequence
 not depend on it).  Before it writes, the tool checks with the project's model (tests/interrupted_model.py) that one (sequence, k)
 of a low-complexity case lists more candidates than len / 4 + 16 and one has more episodes than len / 4 + 64 (the room the one-lane
 engine gives a lane), and that the 64-long unit is reported with phase 63 varying.
+
+--by-k writes tests/golden/interrupted_by_k.jsonl.gz: a budget per motif size, RepeatTracker(k, ..., m_k, ...) in the
+same driver.  800 cases of at most 600 positions from make_case(), each with a vector of budgets 0-3 from a small palette per range
+of motif sizes (at least a third of all budgets are 0, some motif sizes have k <= m_k), and 8 cases of 5-10 kb (by_k_long_cases()):
+random ACGT with planted units, two letters, an N block with lower case, and units of 16-64 under k 16-64 with budgets 0 and 2
+alternating.  At most 40 distinct (settings, vector), so that a test can hand all cases of one to one call.  Before it writes, the
+tool checks with the project's model that at least half of the cases have rows that differ from those under the uniform budget
+max(m_k): otherwise the fixture would show nothing.  The settings of these cases hold "max_interruptions_by_k", a list with one
+entry per motif size, in place of "max_interruptions".
 
 Each line: {"tag", "seq", "settings": {min_motif_size, max_motif_size, min_repeats, min_span, max_interruptions},
 "rows": [[start, end, motif], ...]} -- the motif with N at the phases that were allowed to vary.
@@ -31,9 +41,11 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "tests", "golden", "interrupted.jsonl.gz")
 LONG_OUT = os.path.join(ROOT, "tests", "golden", "interrupted_long.jsonl.gz")
+BY_K_OUT = os.path.join(ROOT, "tests", "golden", "interrupted_by_k.jsonl.gz")
 
 
 def reference_rows(RepeatTracker, seq, kmin, kmax, min_repeats, min_span, max_interruptions):
+    """max_interruptions: one number, or a list with the budget of every motif size kmin .. kmax."""
     s = seq.upper()
     lo, hi = 0, len(s)
     while lo < hi and s[lo] == "N":
@@ -43,7 +55,8 @@ def reference_rows(RepeatTracker, seq, kmin, kmax, min_repeats, min_span, max_in
     s = s[lo:hi]
     out = {}
     for k in range(kmin, kmax + 1):
-        t = RepeatTracker(motif_size=k, min_repeats=min_repeats, min_span=min_span, max_interruptions=max_interruptions,
+        m = max_interruptions[k - kmin] if isinstance(max_interruptions, list) else max_interruptions
+        t = RepeatTracker(motif_size=k, min_repeats=min_repeats, min_span=min_span, max_interruptions=m,
                           input_sequence=s, output_intervals=out)
         while t.advance():
             pass
@@ -224,6 +237,117 @@ def check_long_cases(cases):
     assert over_eps, "no (sequence, k) of a low-complexity case has more than len / 4 + 64 episodes"
 
 
+# ---- a budget per motif size (--by-k) ----
+
+def by_k_palette(rng):
+    """{(kmin, kmax): [vector, ...]}: four vectors per small range, two for 16-64, budgets 0-3 with 0 twice as likely as each
+    other value; the first vector of every small range is the staircase (0 for k 1-2, 1 for 3-4, 2 above), and every range has a
+    vector with some k <= m_k."""
+    pal = {}
+    for kmin, kmax in SMALL_K + LARGE_K:
+        nk = kmax - kmin + 1
+        want = 2 if (kmin, kmax) in LARGE_K else 4
+        vs = [] if (kmin, kmax) in LARGE_K else [[0 if k <= 2 else 1 if k <= 4 else 2 for k in range(kmin, kmax + 1)]]
+        while len(vs) < want:
+            v = [rng.choice([0, 0, 1, 2, 3]) for _ in range(nk)]
+            absorbing = any(kmin + j <= m for j, m in enumerate(v))
+            if v in vs or 3 * v.count(0) < nk or not any(v) or (kmin <= 3 and len(vs) == 1 and not absorbing):
+                continue
+            vs.append(v)
+        pal[(kmin, kmax)] = vs
+    return pal
+
+
+def by_k_long_cases(rng, pal):
+    cases = []
+
+    def add(tag, seq, kmin, kmax, r, span, vec):
+        cases.append({"tag": tag, "seq": seq, "settings": {"min_motif_size": kmin, "max_motif_size": kmax, "min_repeats": r,
+                                                          "min_span": span, "max_interruptions_by_k": list(vec)}})
+
+    def acgt(n):
+        s = list(random_seq(rng, n, "ACGT"))
+        plant_into(rng, s, n // 500, (1, 8), (3, 20), (0, 3))
+        return "".join(s)
+
+    stairs = pal[(1, 6)][0]
+    add("random_planted", acgt(8_000), 1, 6, 3, 9, stairs)
+    add("random_planted", acgt(10_000), 2, 8, 2, 5, pal[(2, 8)][1])
+    add("random_planted", acgt(5_000), 1, 6, 2, 5, pal[(1, 6)][1])
+    add("random_planted", acgt(10_000), 1, 6, 3, 9, [1, 2, 0, 0, 3, 0])       # k 1 and 2 absorb (k <= m_k), 3, 4 and 6 may not vary
+    add("two_letters", random_seq(rng, 5_000, "AC"), 1, 6, 2, 5, stairs)
+    add("two_letters", random_seq(rng, 6_000, "AT"), 2, 8, 3, 9, pal[(2, 8)][0])
+    body = acgt(10_000)
+    add("n_block_lower", "NN" + body[:4_000] + "N" * 300 + body[4_300:7_000].lower() + "n" * 40 + body[7_040:] + "N" * 7, 1, 6, 3, 9, stairs)
+    s = list(random_seq(rng, 5_000, "ACGT"))
+    plant_into(rng, s, 12, (16, 64), (2, 5), (0, 4))
+    add("large_k_alternating", "".join(s), 16, 64, 2, 5, [0 if k % 2 == 0 else 2 for k in range(16, 65)])
+    return cases
+
+
+def by_k_cases(seed, n_short):
+    rng = random.Random(seed)
+    pal = by_k_palette(rng)
+    cases = []
+    for i in range(n_short):
+        case = make_case(rng, i)
+        st = case["settings"]
+        del st["max_interruptions"]
+        st["max_interruptions_by_k"] = list(rng.choice(pal[(st["min_motif_size"], st["max_motif_size"])]))
+        cases.append(case)
+    return cases + by_k_long_cases(rng, pal)
+
+
+def check_by_k_cases(cases):
+    """What the fixture is for, checked with the project's model before the reference runs."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import interrupted_by_k_model as K
+    import interrupted_model as M
+    groups = {json.dumps(c["settings"], sort_keys=True) for c in cases}
+    assert len(groups) <= 40, f"{len(groups)} distinct (settings, vector)"
+    budgets = [(c["settings"]["min_motif_size"] + j, m) for c in cases for j, m in enumerate(c["settings"]["max_interruptions_by_k"])]
+    assert all(0 <= m <= 3 for _k, m in budgets)
+    assert 3 * sum(m == 0 for _k, m in budgets) >= len(budgets), "fewer than a third of the budgets are 0"
+    assert sum(k <= m for k, m in budgets) > len(cases) // 20, "hardly any motif size with k <= m_k"
+    assert sum(5_000 <= len(c["seq"]) <= 10_400 for c in cases) == 8 and all(len(c["seq"]) <= 600 or len(c["seq"]) >= 5_000 for c in cases)
+    differ = 0
+    for c in cases:
+        st = c["settings"]
+        p = (c["seq"], st["min_motif_size"], st["max_motif_size"], st["min_repeats"], st["min_span"])
+        vec = st["max_interruptions_by_k"]
+        differ += K.detect(*p, vec, stride=8, slots=1 << 16) != M.detect(*p, max(vec), stride=8, slots=1 << 16)
+    assert 2 * differ >= len(cases), f"only {differ} of {len(cases)} cases differ from the uniform budget max(m_k)"
+    return differ, len(groups)
+
+
+def _by_k_rows(case):
+    st = case["settings"]
+    return reference_rows(_TRACKER, case["seq"], st["min_motif_size"], st["max_motif_size"], st["min_repeats"], st["min_span"],
+                          st["max_interruptions_by_k"])
+
+
+def write_by_k(RepeatTracker, seed, n_short, out, jobs):
+    global _TRACKER
+    import multiprocessing
+    _TRACKER = RepeatTracker
+    cases = by_k_cases(seed, n_short)
+    differ, groups = check_by_k_cases(cases)
+    order = sorted(range(len(cases)), key=lambda i: -len(cases[i]["seq"]))      # the long ones first
+    if jobs > 1:
+        with multiprocessing.get_context("fork").Pool(jobs) as pool:
+            rows = pool.map(_by_k_rows, [cases[i] for i in order], chunksize=1)
+    else:
+        rows = [_by_k_rows(cases[i]) for i in order]
+    for i, r in zip(order, rows):
+        cases[i]["rows"] = r
+    with open(out, "wb") as raw, gzip.GzipFile(fileobj=raw, mode="wb", filename="", mtime=0) as f:
+        for case in cases:
+            f.write((json.dumps(case, separators=(",", ":")) + "\n").encode())
+    size = os.path.getsize(out)
+    assert size < os.path.getsize(LONG_OUT), f"{size} bytes: not below interrupted_long.jsonl.gz"
+    print(f"wrote {len(cases)} cases ({groups} distinct settings, {differ} differ from the uniform budget max(m_k)) to {out} ({size} bytes)")
+
+
 _TRACKER = None
 
 
@@ -254,11 +378,12 @@ def write_long(RepeatTracker, seed, out, jobs):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reference", required=True, help="checkout of the reference repository (holds utils/repeat_tracker.py)")
-    ap.add_argument("--cases", type=int, default=3200)
-    ap.add_argument("--seed", type=int, default=None, help="default: 9, with --long 17")
+    ap.add_argument("--cases", type=int, default=None, help="default: 3200, with --by-k 800 (short cases)")
+    ap.add_argument("--seed", type=int, default=None, help="default: 9, with --long 17, with --by-k 31")
     ap.add_argument("--out", default=None)
     ap.add_argument("--long", action="store_true", help="write the long fixture (interrupted_long.jsonl.gz) instead")
-    ap.add_argument("--jobs", type=int, default=4, help="--long: processes that run the reference")
+    ap.add_argument("--by-k", action="store_true", help="write the fixture with a budget per motif size (interrupted_by_k.jsonl.gz) instead")
+    ap.add_argument("--jobs", type=int, default=4, help="--long, --by-k: processes that run the reference")
     args = ap.parse_args()
     sys.dont_write_bytecode = True
     sys.path.insert(0, os.path.abspath(args.reference))
@@ -266,7 +391,12 @@ def main():
     if args.long:
         write_long(RepeatTracker, 17 if args.seed is None else args.seed, args.out or LONG_OUT, args.jobs)
         return
+    if args.by_k:
+        write_by_k(RepeatTracker, 31 if args.seed is None else args.seed, 800 if args.cases is None else args.cases,
+                   args.out or BY_K_OUT, args.jobs)
+        return
     args.seed = 9 if args.seed is None else args.seed
+    args.cases = 3200 if args.cases is None else args.cases
     args.out = args.out or OUT
     rng = random.Random(args.seed)
     with gzip.open(args.out, "wt") as f:
