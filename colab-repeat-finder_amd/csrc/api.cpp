@@ -87,6 +87,17 @@ static launch_view active_launch(const prf_genome *g) {
     return launch_view{g->vp.launch_list, g->vp.n_launch, g->vp.flat_base, g->positions};
 }
 
+int prf_genome_contig_view(const prf_genome *g, u32 contig, prf_contig_view *out) {
+    if (!g || !out) return fail(PRF_EINVAL, "NULL genome");
+    if (contig >= g->base.size()) return fail(PRF_EINVAL, "contig %u out of range (the genome holds %zu)", contig, g->base.size());
+    out->ctx = g->ctx;
+    out->planes = prf_planes{g->H, g->L, g->X, {g->E[0], g->E[1], g->E[2], g->E[3], g->E[4]}};
+    out->base = g->base[contig];
+    out->len = g->len[contig];
+    out->kmax_hint = g->kmax_hint;
+    return PRF_OK;
+}
+
 extern "C" {
 
 int prf_abi_version(void) { return PRF_ABI_VERSION; }

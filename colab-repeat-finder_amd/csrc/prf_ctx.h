@@ -46,6 +46,15 @@ static int check_params(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, u32 k
     return PRF_OK;
 }
 
+// One contig of a resident genome as the host paths outside api.cpp see it (the genome's own struct stays private to api.cpp)
+struct prf_contig_view {
+    prf_ctx *ctx;
+    prf_planes planes;  // linear planes; at least kmax_hint / 64 + 8 readable words behind them
+    u64 base, len;      // first global position, positions
+    u32 kmax_hint;
+};
+__attribute__((visibility("hidden"))) int prf_genome_contig_view(const prf_genome *g, u32 contig, prf_contig_view *out);
+
 // A device array that lives as long as its scope.  alloc(0) still allocates, so that p is always an address a copy of nothing
 // or a kernel over nothing may be given; what the array held before is freed, not kept.
 template <class T>

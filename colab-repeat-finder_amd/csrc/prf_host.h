@@ -126,3 +126,21 @@ struct prf_int_emit_args {
 hipError_t prf_launch_int_emit(hipStream_t s, const prf_int_emit_args &a);
 size_t prf_int_sort_scratch_bytes(u64 n);
 hipError_t prf_int_sort_rows(hipStream_t s, const prf_ihit_dev *rows, u64 n, prf_ihit_dev *out, void *scratch);
+
+// periodicity matrix (periodicity.hip): cells seq[i] == seq[i + k] of `len` positions from global position g_begin,
+// for k = kmin .. kmax; N == N matches, nothing at or behind g_begin + len is compared (or read)
+struct prf_periodicity_args {
+    prf_planes pl;
+    u64 g_begin, len;
+    u64 n_words;      // ceil(len / 64)
+    u64 n_windows;    // counts: ceil(n_words / wpw)
+    u32 kmin, kmax;
+    u32 wpw;          // counts: words per window (window / 64); bits: 1
+    u64 *bits;        // want_bits: (kmax - kmin + 1) x n_words words, every one written
+    u32 *counts;      // otherwise: (kmax - kmin + 1) x n_windows sums, zeroed by the caller
+    u32 span_words, kslice, lds_stride;  // set by the launch wrapper (prf_periodicity_shape)
+};
+#define PRF_PER_LDS_BYTES 65536u
+// words of the range per workgroup, motif sizes per slice, LDS words per plane
+void prf_periodicity_shape(bool exotic, u32 *span_words, u32 *kslice, u32 *lds_stride);
+hipError_t prf_launch_periodicity(hipStream_t s, prf_periodicity_args a, bool want_bits);

@@ -255,7 +255,7 @@ def _build_parser():
                    help="With --max-interruptions > 0: positions of a sequence that one GPU lane walks (default: the library's, "
                         "2^20; 0: one lane per motif size).  The output does not depend on it.")
     p.add_argument("-i", "--interval", help="Restrict the scan to chrom:start_0based-end.")
-    p.add_argument("-p", "--plot", help="Accepted for compatibility; plotting is not part of this build.")
+    p.add_argument("-p", "--plot", help="Write out a plot with this filename (a literal input sequence of at most 5,000 bp).")
     p.add_argument("-o", "--output-prefix", help="Prefix of the output TSV (and BED, for FASTA input).")
     p.add_argument("--verbose", action="store_true", help="Print verbose output.")
     p.add_argument("--debug", action="store_true", help="Print debugging output.")
@@ -527,8 +527,12 @@ def _scan_literal(args, parser):
         tsv.write("start_0based\tend\tmotif\n")
         tsv.writelines(f"{s}\t{e}\t{m}\n" for s, e, m in rows)
     print(f"Wrote results to {tsv_path}")
-    if args.plot:
-        print("Warning: --plot is not implemented in this build. Skipping plot...")
+    if args.plot:                       # reference :175-179: literal sequences only; a FASTA input plots nothing, silently
+        if len(args.input_sequence) > 5_000:
+            print(f"Warning: The input sequence is too long ({len(args.input_sequence):,d} bp). Skipping plot...")
+        else:
+            from utils.plot_utils import plot_results
+            plot_results(args.input_sequence, rows, args.max_motif_size, args.plot)
 
 
 def main(argv=None):

@@ -114,6 +114,8 @@ EXPORTS = ["prf_abi_version", "prf_device_count", "prf_last_error", "prf_open", 
            "prf_genome_contig_bases", "prf_scan_literal", "prf_scan_genome_async_packed", "prf_stream_wait_for",
            "prf_genome_footprint", "prf_scan_interrupted", "prf_scan_interrupted_ex", "prf_free_ihits",
            "prf_scan_interrupted_chunked", "prf_scan_interrupted_by_k"]
+# the periodicity entry points (include/prf_period.h, which prf.h includes)
+PERIOD_EXPORTS = ["prf_period_counts", "prf_period_bits", "prf_period_counts_seq", "prf_period_bits_seq"]
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -191,6 +193,15 @@ def load_library():
             ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(_IHits),
             ctypes.POINTER(ScanStats), ctypes.POINTER(ctypes.c_uint64)]
         lib.prf_free_ihits.argtypes = [ctypes.POINTER(_IHits)]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        lib.prf_period_counts.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                          ctypes.c_uint64, vp, ctypes.c_uint64, u64p, ctypes.POINTER(ScanStats)]
+        lib.prf_period_bits.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                        vp, ctypes.c_uint64, u64p, ctypes.POINTER(ScanStats)]
+        lib.prf_period_counts_seq.argtypes = [vp, ctypes.POINTER(_Contig), ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                              ctypes.c_uint32, ctypes.c_uint64, vp, ctypes.c_uint64, u64p, ctypes.POINTER(ScanStats)]
+        lib.prf_period_bits_seq.argtypes = [vp, ctypes.POINTER(_Contig), ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                            ctypes.c_uint32, vp, ctypes.c_uint64, u64p, ctypes.POINTER(ScanStats)]
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
         lib.prf_measure_hbm_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -256,13 +267,65 @@ def _rows(hits):
     return rec
 
 
+END_OF_CONTIG = (1 << 64) - 1   # period_counts / period_bits: `end` beyond any contig, clipped by the library to its length
+
+
+def _period_check(kmin, kmax, window):
+    if kmin < 1 or kmax < kmin:
+        raise ValueError(f"motif sizes {kmin} .. {kmax}: an empty range")
+    if window is not None and (window < 64 or window % 64):
+        raise ValueError(f"window is {window}. It must be a multiple of 64, at least 64.")
+
+
+def _period_call(lib, kmin, kmax, window, length, call):
+    """The output array of a periodicity call on `length` positions (after clipping), filled by call(dst, capacity, n_out,
+    stats): uint32[nk, windows] for a window, uint64[nk, words] for window None.  Returns (array, stats)."""
+    import numpy as np
+    nk = kmax - kmin + 1
+    unit = 64 if window is None else window
+    per_k = -(-length // unit)
+    out = np.zeros(max(1, nk * per_k), dtype=np.uint64 if window is None else np.uint32)
+    n_out, stats = ctypes.c_uint64(0), ScanStats()
+    _check(lib, call(out.ctypes.data_as(ctypes.c_void_p), nk * per_k, ctypes.byref(n_out), ctypes.byref(stats)))
+    assert n_out.value == per_k, (n_out.value, per_k)
+    return out[:nk * per_k].reshape(nk, per_k), stats
+
+
 class Genome:
     """Contigs packed and resident in HBM (prf_genome)."""
 
-    def __init__(self, ctx, handle, n_contigs):
+    def __init__(self, ctx, handle, n_contigs, lens=None):
         self.ctx = ctx
         self._h = handle
         self.n_contigs = n_contigs
+        self.lens = None if lens is None else [int(n) for n in lens]   # contig lengths (period_counts / period_bits clip by them)
+
+    def _period(self, contig, kmin, kmax, window, begin, end, with_stats):
+        _period_check(kmin, kmax, window)
+        if self.lens is None or not 0 <= contig < len(self.lens):
+            raise ValueError(f"contig {contig}: the genome holds {self.n_contigs}")
+        stop = self.lens[contig] if end is None else min(end, self.lens[contig])
+        if begin < 0 or begin > (stop if end is None else end):
+            raise ValueError(f"begin {begin} is behind end {stop if end is None else end}")
+        lib, c_end = self.ctx.lib, END_OF_CONTIG if end is None else end
+        if window is None:
+            call = lambda dst, cap, n, st: lib.prf_period_bits(self.ctx._h, self._h, contig, begin, c_end, kmin, kmax, dst, cap, n, st)
+        else:
+            call = lambda dst, cap, n, st: lib.prf_period_counts(self.ctx._h, self._h, contig, begin, c_end, kmin, kmax, window,
+                                                                 dst, cap, n, st)
+        out, stats = _period_call(lib, kmin, kmax, window, max(0, stop - begin), call)
+        return (out, stats) if with_stats else out
+
+    def period_counts(self, contig, kmin, kmax, window, begin=0, end=None, with_stats=False):
+        """The periodicity profile of positions [begin, end) of a contig (prf_period_counts): numpy uint32[kmax - kmin + 1,
+        ceil(length / window)]; entry (k - kmin, w) = the positions i of window w with seq[i] == seq[i + k], i + k < end (N == N
+        matches).  window: a multiple of 64.  end None or beyond the contig: its length.  with_stats: (array, ScanStats)."""
+        return self._period(contig, kmin, kmax, window, begin, end, with_stats)
+
+    def period_bits(self, contig, kmin, kmax, begin=0, end=None, with_stats=False):
+        """The periodicity matrix itself (prf_period_bits): numpy uint64[kmax - kmin + 1, ceil(length / 64)]; bit j of word w of
+        row k - kmin = seq[i] == seq[i + k] for i = begin + 64 w + j, i + k < end."""
+        return self._period(contig, kmin, kmax, None, begin, end, with_stats)
 
     @property
     def positions(self):
@@ -360,7 +423,7 @@ class Context:
         arr, _keep = _contig_array(seqs)
         g = ctypes.c_void_p()
         _check(self.lib, self.lib.prf_genome_load(self._h, arr, len(seqs), kmax_hint, ctypes.byref(g)))
-        return Genome(self, g, len(seqs))
+        return Genome(self, g, len(seqs), [s[1] if isinstance(s, tuple) else len(s) for s in seqs])
 
     def synth(self, lens, seeds, kmax_hint):
         """Contigs generated on the device (SURVEY 8(d) generator): nothing crosses PCIe."""
@@ -369,7 +432,7 @@ class Context:
         sa = (ctypes.c_uint64 * max(1, n))(*seeds)
         g = ctypes.c_void_p()
         _check(self.lib, self.lib.prf_genome_synth(self._h, la, sa, n, kmax_hint, ctypes.byref(g)))
-        return Genome(self, g, n)
+        return Genome(self, g, n, lens)
 
     def standin(self, lens, seeds, kmax_hint):
         """Contigs of the stand-in recipe 2 (synth.standin2) generated on the device."""
@@ -378,7 +441,7 @@ class Context:
         sa = (ctypes.c_uint64 * max(1, n))(*seeds)
         g = ctypes.c_void_p()
         _check(self.lib, self.lib.prf_genome_standin(self._h, la, sa, n, kmax_hint, ctypes.byref(g)))
-        return Genome(self, g, n)
+        return Genome(self, g, n, lens)
 
     def scan(self, seqs, kmin, kmax, min_repeats, min_span, flags=SCAN_DEFAULT):
         arr, _keep = _contig_array(seqs)
@@ -435,6 +498,30 @@ class Context:
                 out.update(lanes=ctr[4], dropped_lanes=ctr[5])
             return rows, stats, out
         return rows, stats
+
+    def _period_seq(self, seq, kmin, kmax, window, begin, end, with_stats):
+        _period_check(kmin, kmax, window)
+        if isinstance(seq, str):
+            seq = seq.encode("ascii", "replace")
+        arr, _keep = _contig_array([seq])
+        stop = len(seq) if end is None else min(end, len(seq))
+        if begin < 0 or begin > (stop if end is None else end):
+            raise ValueError(f"begin {begin} is behind end {stop if end is None else end}")
+        lib, c_end = self.lib, END_OF_CONTIG if end is None else end
+        if window is None:
+            call = lambda dst, cap, n, st: lib.prf_period_bits_seq(self._h, arr, begin, c_end, kmin, kmax, dst, cap, n, st)
+        else:
+            call = lambda dst, cap, n, st: lib.prf_period_counts_seq(self._h, arr, begin, c_end, kmin, kmax, window, dst, cap, n, st)
+        out, stats = _period_call(lib, kmin, kmax, window, max(0, stop - begin), call)
+        return (out, stats) if with_stats else out
+
+    def period_counts(self, seq, kmin, kmax, window, begin=0, end=None, with_stats=False):
+        """Genome.period_counts for one sequence (str or bytes) in one call: load, count, free (prf_period_counts_seq)."""
+        return self._period_seq(seq, kmin, kmax, window, begin, end, with_stats)
+
+    def period_bits(self, seq, kmin, kmax, begin=0, end=None, with_stats=False):
+        """Genome.period_bits for one sequence (str or bytes) in one call (prf_period_bits_seq)."""
+        return self._period_seq(seq, kmin, kmax, None, begin, end, with_stats)
 
     def scan_literal(self, seq, kmin, kmax, min_repeats, min_span, stop=None):
         """The literal lane on one sequence (prf_scan_literal); stop: lock-step iterations performed, default all."""

@@ -82,7 +82,7 @@ typedef struct prf_scan_stats {
     uint64_t n_candidates;  /* phase-1 candidates                                                        */
     uint64_t n_hits;        /* rows                                                                      */
     uint32_t n_launches;    /* kernel launches in the timed region                                       */
-    uint32_t path;          /* 0 = generic kernel, 1 = vertical bit-sliced kernel, 2 = literal lane, 3 = interrupted */
+    uint32_t path;          /* 0 = generic kernel, 1 = vertical bit-sliced kernel, 2 = literal lane, 3 = interrupted, 4 = periodicity */
     uint64_t seq;           /* fused path: serial number of this scan on its context (prf_scan_timings)  */
     uint32_t sorted_on_device; /* 1: the rows left the device sorted by (contig, start, end), no host sort   */
     uint32_t tiles_launched;   /* fused path: 65536-position tiles scanned (tiles of nothing but N are skipped)     */
@@ -229,6 +229,10 @@ int prf_scan_interrupted_by_k(prf_ctx *ctx, const prf_contig *contigs, int n_con
                               uint64_t memo_slots, uint64_t chunk, prf_ihits *out, prf_scan_stats *stats, uint64_t *counters);
 void prf_free_ihits(prf_ihits *hits);
 
+/* ---- periodicity matrix and windowed period counts (the reference's get_period_matrix, utils/plot_utils.py:12-25) on a
+ * resident genome: four more entry points of this library, additions to ABI version 4, declared in prf_period.h, which this
+ * header includes below; prf_scan_stats.path = 4 is theirs. */
+
 /* Pipelined scans.  prf_scan_genome_async() enqueues a scan and returns its serial number at once;
  * prf_scan_wait() collects it (row count and candidate count in *stats; kernel time through prf_scan_timings;
  * rows through prf_last_hits_to_device, valid until the next-but-one scan is enqueued).  At most two scans are in
@@ -319,6 +323,8 @@ int prf_plan_describe(uint32_t kmin, uint32_t kmax, uint32_t min_repeats, uint32
 
 /* Roofline probe: streaming 16-byte-per-lane read of `bytes` bytes, best of `iters`; GB/s (1e9). */
 int prf_measure_hbm_read(prf_ctx *ctx, uint64_t bytes, int iters, double *gbps);
+
+#include "prf_period.h"
 
 #ifdef __cplusplus
 }
