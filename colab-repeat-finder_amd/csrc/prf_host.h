@@ -144,3 +144,23 @@ struct prf_periodicity_args {
 // words of the range per workgroup, motif sizes per slice, LDS words per plane
 void prf_periodicity_shape(bool exotic, u32 *span_words, u32 *kslice, u32 *lds_stride);
 hipError_t prf_launch_periodicity(hipStream_t s, prf_periodicity_args a, bool want_bits);
+
+// dot plot (dotplot.hip): kept cells (s[i] == s[j], filtered by diagonal runs) of window rows x columns of the
+// n x n matrix of the n positions from global position g_begin; N == N matches, nothing at or behind g_begin + n is compared
+// (or read), runs are judged on the whole matrix
+struct prf_dotplot_args {
+    prf_planes pl;
+    u64 g_begin, n;
+    u64 row0, col0, col1;   // the window (clipped to n); its rows end with lrow1 of the last launch
+    u64 lrow0, lrow1;       // rows of this launch: lrow0 - row0 is a multiple of tile_rows
+    u64 words_per_row;      // ceil((col1 - col0) / 64)
+    u32 m;                  // cells a run must have: max(min_diagonal_run - 1, 1)
+    u32 wpb;                // counts: words per block (block / 64)
+    u64 n_block_cols;       // counts: ceil(words_per_row / wpb)
+    u64 *bits;              // want_bits: rows x words_per_row words, every one written
+    u32 *counts;            // otherwise: block rows x n_block_cols sums, zeroed by the caller
+    u32 tile_rows, span_words, halo, n_spans;  // set by the launch wrapper (prf_dotplot_shape_for)
+};
+// rows per workgroup tile, words of 64 columns per workgroup span, halo rows above and below (= m - 1); the same for 3 and 8 planes
+void prf_dotplot_shape_for(u32 min_diagonal_run, u32 *tile_rows, u32 *span_words, u32 *halo);
+hipError_t prf_launch_dotplot(hipStream_t s, prf_dotplot_args a, bool want_bits);

@@ -1,0 +1,272 @@
+"""Plot the dot plot of a DNA sequence (reference plot_dot_plot.py), computed on the GPU: pixel (i, j) is dark if positions i and
+j hold the same base and the pixel lies on a diagonal or anti-diagonal run of dark pixels of at least --filter-threshold - 1.
+
+The reference's arguments, for sequences of at most 5,000 positions (one pixel per cell):
+    plot_dot_plot.py CAGCAGCAGCAGTTTCTGCTGCTG -o dots.png
+    plot_dot_plot.py -R genome.fa chr22:1000-3000 regions.bed -p 50 -d plots --show-filtered-pixels
+Beyond the reference: --block B turns the plot into a density image -- one pixel per block of B x B cells, grey = kept cells /
+cells of the block -- which has no such limit, and --tsv writes the counts:
+    plot_dot_plot.py -R genome.fa chr22:20000000-21000000 --block 1024 --tsv density.tsv -o density.png
+"""
+import argparse
+import gzip
+import os
+import sys
+
+import numpy as np
+
+MAX_MATRIX_POSITIONS = 5_000   # one pixel per cell up to here (the limit of perfect_repeat_finder.py -p); above it: --block
+
+
+def parse_interval(interval_string):
+    """"chr1:12345-54321" -> (chrom, start, end); the chromosome name may itself hold colons."""
+    try:
+        chrom, _, span = interval_string.rpartition(":")
+        start, end = (int(v) for v in span.split("-"))
+    except Exception as e:
+        raise ValueError(f"Unable to parse interval: '{interval_string}': {e}")
+    return chrom, start, end
+
+
+def _context(context):
+    if context is not None:
+        return context
+    import prf_native
+    return prf_native.default_context()
+
+
+def dot_plot_matrix(sequence, min_diagonal_run=3, set_noise_to=0, context=None):
+    """numpy uint8[n, n]: 1 where the reference's generate_matrix + filter_out_noise(min_diagonal_run) leave a 1, set_noise_to
+    where they put set_noise_to, 0 elsewhere -- from the GPU: one call at min_diagonal_run, and one more without a filter if
+    the filtered-out cells are wanted."""
+    import prf_native
+    n = len(sequence)
+    ctx = _context(context)
+    kept = prf_native.unpack_bits(ctx.dotplot_bits(sequence, min_diagonal_run), n)
+    if not set_noise_to or min_diagonal_run <= 2:
+        return kept
+    raw = prf_native.unpack_bits(ctx.dotplot_bits(sequence, 0), n)
+    return (kept + set_noise_to * (raw & ~kept & 1)).astype(np.uint8)
+
+
+def generate_matrix(sequence, context=None):
+    """The square list of lists with entry (i, j) == 1 if sequence[i] == sequence[j] (compared in upper case), else 0."""
+    return dot_plot_matrix("".join(sequence), 0, context=context).tolist()
+
+
+def is_noise(matrix, i, j, min_diagonal_run=3):
+    """True unless (i, j) lies on a stretch of cells > 0 along one of the two diagonals that is long enough: the cell counts in
+    both directions of a diagonal, so a stretch of L cells passes if L + 1 >= min_diagonal_run."""
+    size = len(matrix)
+
+    def reach(di, dj):
+        steps, a, b = 0, i, j
+        while 0 <= a < size and 0 <= b < size and matrix[a][b] > 0:
+            a, b, steps = a + di, b + dj, steps + 1
+        return steps
+
+    if not (0 <= i < size and 0 <= j < size and matrix[i][j] > 0):
+        return True
+    return all(reach(1, dj) + reach(-1, -dj) < min_diagonal_run for dj in (1, -1))
+
+
+def _long_enough(cells, m):
+    """bool matrix: the cell is set and lies on a run of at least m set cells along (+1, +1)."""
+    n_rows, n_cols = cells.shape
+    total = np.zeros(cells.shape, dtype=np.int32)
+    for sign in (1, -1):
+        alive = cells.copy()
+        total += alive
+        for v in range(1, m):
+            moved = np.zeros_like(cells)
+            if v < n_rows and v < n_cols:
+                if sign > 0:
+                    moved[:-v, :-v] = cells[v:, v:]
+                else:
+                    moved[v:, v:] = cells[:-v, :-v]
+            alive &= moved
+            if not alive.any():
+                break
+            total += alive
+    return cells & (total - 1 >= m)
+
+
+def filter_out_noise(matrix, min_diagonal_run=3, set_noise_to=0):
+    """Filters a 0/1 matrix (list of lists or numpy array) in place as the reference does: a cell > 0 that is_noise() becomes
+    set_noise_to.  The reference's row-major in-place loop leaves exactly the cells whose diagonal or anti-diagonal stretch in
+    the UNFILTERED matrix has L + 1 >= min_diagonal_run; that closed form is computed here with numpy."""
+    cells = np.asarray(matrix) > 0
+    if cells.size == 0 or min_diagonal_run <= 2:
+        return
+    m = min_diagonal_run - 1
+    kept = _long_enough(cells, m) | _long_enough(cells[:, ::-1], m)[:, ::-1]
+    noise = cells & ~kept
+    if isinstance(matrix, np.ndarray):
+        matrix[noise] = set_noise_to
+        return
+    for i in np.flatnonzero(noise.any(axis=1)).tolist():
+        row = matrix[i]
+        for j in np.flatnonzero(noise[i]).tolist():
+            row[j] = set_noise_to
+
+
+PALETTE = ("white", "black", "red")     # cell values 0 (empty), 1 (kept), 2 (filtered out, --show-filtered-pixels)
+
+
+def _draw(image, save_path, show, figure_size, **imshow):
+    """One square image without ticks, with a thin grey frame, cropped to the axes when saved."""
+    import matplotlib
+    if not show:
+        matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    fig, ax = plt.subplots(figsize=(figure_size, figure_size))
+    if len(image):
+        ax.imshow(image, interpolation="nearest", **imshow)
+    ax.tick_params(left=False, bottom=False, labelleft=False, labelbottom=False)
+    for side in ("left", "right", "top", "bottom"):
+        ax.spines[side].set(color="#CCCCCC", linewidth=0.5)
+    if show:
+        plt.show()
+    if save_path:
+        fig.savefig(save_path, bbox_inches="tight", pad_inches=0)
+    plt.close(fig)
+
+
+def plot_dot_plot(matrix, save_path=None, show=False, figure_size=None):
+    """Draw the matrix as a square image: 0 white, 1 black, 2 (filtered-out cells) red.  figure_size (inches) defaults to the
+    reference's 5 * len(matrix) / 150."""
+    from matplotlib.colors import ListedColormap
+    size = len(matrix)
+    top = int(np.max(matrix)) if size else 0
+    _draw(matrix, save_path, show, max(5 * size / 150, 0.2) if figure_size is None else figure_size,
+          cmap=ListedColormap(list(PALETTE[:top + 1])), vmin=0, vmax=top)
+
+
+def plot_density(counts, block, n, save_path=None, show=False, figure_size=None):
+    """Draw block counts (dotplot_counts of an n x n matrix) as a grey image: kept cells / cells of the (clipped) block."""
+    edge = np.minimum(block, n - block * np.arange(counts.shape[0])).astype(np.float64)
+    density = counts / np.outer(edge, edge)
+    _draw(density, save_path, show, min(max(5 * counts.shape[0] / 150, 2.0), 40.0) if figure_size is None else figure_size,
+          cmap="gray_r", vmin=0.0, vmax=1.0)
+
+
+def density_lines(name, begin, n, block, counts):
+    """The --tsv lines: name, row start, row end, column start, column end, kept cells; one line per block with a kept cell."""
+    for r, c in zip(*(v.tolist() for v in counts.nonzero())):
+        yield (f"{name}\t{begin + r * block}\t{begin + min(n, (r + 1) * block)}\t{begin + c * block}\t"
+               f"{begin + min(n, (c + 1) * block)}\t{int(counts[r, c])}\n")
+
+
+def build_parser():
+    """The reference's options and positionals (names as there, so that its command lines run unchanged), plus --block / --tsv."""
+    p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    p.add_argument("-w", "--image-size", type=float, help="side of the square image, in inches (default: 5/150 inch per cell)")
+    p.add_argument("-d", "--output-dir", default=".", help="directory the images go to; created if missing")
+    p.add_argument("-o", "--output-path", default="dot_plot.png", help="file name of the image when there is exactly one input")
+    p.add_argument("-t", "--filter-threshold", type=int, default=3,
+                   help="min_diagonal_run of the noise filter, 0 to 64: a cell stays if its diagonal or anti-diagonal run has "
+                        "at least this many cells minus one; 2 or less keeps every cell")
+    p.add_argument("-p", "--padding", type=int, default=0, help="widen every interval by this many positions on both sides")
+    p.add_argument("--show-filtered-pixels", action="store_true", help="draw the cells the filter removed in red")
+    p.add_argument("--show-plot", action="store_true", help="open each image in a window as well")
+    p.add_argument("-R", "--reference-fasta", help="FASTA file that intervals and BED lines refer to")
+    p.add_argument("-v", "--verbose", action="store_true", help="report every sequence as it is plotted")
+    p.add_argument("--block", type=int, help="Plot the density instead: one pixel per block of this many x this many cells (a "
+                                             "multiple of 64, at most 32768). Needed above 5,000 positions.")
+    p.add_argument("--tsv", help="With --block: also write the block counts as a table.")
+    p.add_argument("input_sequence_or_intervals_or_bed_files", nargs="+",
+                   help="any mix of literal ACGT sequences, intervals chrom:start_0based-end, and BED files")
+    return p
+
+
+def _fetch(parser, fasta_path, cache, chrom, start, end):
+    """(name in the file, sequence[start:end] in upper case): the name as given, or with / without a "chr" prefix."""
+    import prf_native
+    bare = chrom.replace("chr", "")
+    for name in (chrom, f"chr{bare}", bare):
+        if name not in cache:
+            entries = prf_native.Fasta(fasta_path, only=name)
+            cache[name] = entries[name].seq if name in entries else None
+        if cache[name] is not None:
+            return name, cache[name][start:end].upper()
+    parser.error(f"Error: {chrom} not found in {fasta_path}")
+
+
+def resolve_inputs(args, parser):
+    """[(name, begin, sequence, output file name)] after the checks that need no GPU; prints what the reference prints."""
+    if not 0 <= args.filter_threshold <= 64:
+        parser.error(f"--filter-threshold is set to {args.filter_threshold}. It must be between 0 and 64.")
+    if args.block is not None and (args.block < 64 or args.block % 64 or args.block > 32768):
+        parser.error(f"--block is set to {args.block}. It must be a multiple of 64, at least 64 and at most 32768.")
+    if args.tsv and args.block is None:
+        parser.error("--tsv writes the block counts: give --block too")
+    inputs = args.input_sequence_or_intervals_or_bed_files
+    out, n_intervals, cache = [], 0, {}
+    for i, text in enumerate(inputs):
+        if not set(text) - set("ACGT"):                               # a literal nucleotide sequence
+            name = args.output_path if len(inputs) == 1 else f"dot_plot_{i + 1:03d}_of_{len(inputs)}.{len(text)}bp_sequence.png"
+            out.append(("sequence", 0, text, os.path.join(args.output_dir, name)))
+            continue
+        if "bed" not in text and not (":" in text and "-" in text):
+            parser.error(f"Error: {text} is not a valid nucleotide sequence, BED file path, or interval")
+        if not args.reference_fasta:
+            parser.error("Error: --reference-fasta is required when the input is a BED file or interval")
+        intervals = []
+        if "bed" in text:
+            if not os.path.isfile(text):
+                parser.error(f"Error: {text} file not found")
+            with (gzip.open if text.endswith("gz") else open)(text, "rt") as bed_file:
+                for line_i, line in enumerate(bed_file):
+                    fields = line.strip().split("\t")
+                    if len(fields) < 3:
+                        parser.error(f"Error: {text} line #{line_i + 1} is invalid: '{line.strip()}'")
+                    intervals.append((fields[0], int(fields[1]), int(fields[2])))
+        else:
+            try:
+                intervals.append(parse_interval(text))
+            except ValueError as e:
+                parser.error(f"Error: {e}")
+        for k, (chrom, start, end) in enumerate(intervals):
+            start, end = max(0, start - args.padding), end + args.padding     # (the reference lets a padded start go negative)
+            name, seq = _fetch(parser, args.reference_fasta, cache, chrom, start, end)
+            out.append((name, start, seq, os.path.join(
+                args.output_dir, f"dot_plot_{k + 1:03d}_of_{len(intervals)}.{name}_{start}-{end}.{len(seq)}bp_sequence.png")))
+        n_intervals += len(intervals)
+    if n_intervals:                                                    # (the reference prints this line always, and crashes
+        print(f"Loaded {n_intervals:,d} interval(s) from {args.reference_fasta}")   # on it when there were only literals)
+    for name, _begin, seq, _path in out:
+        if args.block is None and len(seq) > MAX_MATRIX_POSITIONS:
+            parser.error(f"The input sequence is too long for one pixel per cell ({len(seq):,d} bp > {MAX_MATRIX_POSITIONS:,d}). "
+                         f"Use --block B (a multiple of 64) to plot the density instead.")
+        if not seq.isalpha() and seq:
+            parser.error(f"Error: the sequence of {name} holds characters that are not letters")
+    if args.tsv and len(out) > 1:
+        parser.error("--tsv takes one input sequence")
+    return out
+
+
+def main(argv=None, context=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    todo = resolve_inputs(args, parser)
+    os.makedirs(args.output_dir, exist_ok=True)
+    for i, (name, begin, seq, path) in enumerate(todo):
+        if args.verbose:
+            print(f"[{i + 1}/{len(todo)}] {name}: {len(seq):,d} positions")
+        if args.block is None:
+            matrix = dot_plot_matrix(seq, args.filter_threshold, 2 if args.show_filtered_pixels else 0, context=context)
+            plot_dot_plot(matrix, save_path=path, show=args.show_plot, figure_size=args.image_size)
+        else:
+            counts = _context(context).dotplot_counts(seq, args.block, args.filter_threshold)
+            plot_density(counts, args.block, len(seq), save_path=path, show=args.show_plot, figure_size=args.image_size)
+            if args.tsv:
+                with open(args.tsv, "wt") as f:
+                    f.writelines(density_lines(name, begin, len(seq), args.block, counts))
+                print(f"Wrote {args.tsv}")
+        if args.verbose or len(todo) == 1:
+            print(f"Wrote {path} ({len(seq):,d} positions)")
+    print(f"{len(todo):,d} dot plot(s) written to {os.path.abspath(args.output_dir)}")
+
+
+if __name__ == "__main__":
+    sys.exit(main())

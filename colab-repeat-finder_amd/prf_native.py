@@ -116,6 +116,12 @@ EXPORTS = ["prf_abi_version", "prf_device_count", "prf_last_error", "prf_open", 
            "prf_scan_interrupted_chunked", "prf_scan_interrupted_by_k"]
 # the periodicity entry points (include/prf_period.h, which prf.h includes)
 PERIOD_EXPORTS = ["prf_period_counts", "prf_period_bits", "prf_period_counts_seq", "prf_period_bits_seq"]
+# the dot-plot entry points (include/prf_dotplot.h, which prf.h includes)
+DOTPLOT_EXPORTS = ["prf_dotplot_bits", "prf_dotplot_counts", "prf_dotplot_bits_ex", "prf_dotplot_counts_ex", "prf_dotplot_bits_seq",
+                   "prf_dotplot_counts_seq", "prf_dotplot_shape"]
+DOT_LAUNCH_CELLS = 1 << 36   # PRF_DOT_LAUNCH_CELLS
+DOT_MAX_CELLS = 1 << 42      # PRF_DOT_MAX_CELLS
+DOT_MAX_RUN = 64             # PRF_DOT_MAX_RUN
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -202,6 +208,16 @@ def load_library():
                                               ctypes.c_uint32, ctypes.c_uint64, vp, ctypes.c_uint64, u64p, ctypes.POINTER(ScanStats)]
         lib.prf_period_bits_seq.argtypes = [vp, ctypes.POINTER(_Contig), ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
                                             ctypes.c_uint32, vp, ctypes.c_uint64, u64p, ctypes.POINTER(ScanStats)]
+        window = [ctypes.c_uint64] * 6 + [ctypes.c_uint32]          # begin, end, row0, row1, col0, col1, min_diagonal_run
+        bits_tail = [vp, ctypes.c_uint64, u64p, ctypes.POINTER(ScanStats)]
+        counts_tail = [ctypes.c_uint64, vp, ctypes.c_uint64, u64p, u64p, ctypes.POINTER(ScanStats)]
+        lib.prf_dotplot_bits.argtypes = [vp, vp, ctypes.c_uint32] + window + bits_tail
+        lib.prf_dotplot_counts.argtypes = [vp, vp, ctypes.c_uint32] + window + counts_tail
+        lib.prf_dotplot_bits_ex.argtypes = [vp, vp, ctypes.c_uint32] + window + bits_tail + [ctypes.c_uint64]
+        lib.prf_dotplot_counts_ex.argtypes = [vp, vp, ctypes.c_uint32] + window + counts_tail + [ctypes.c_uint64]
+        lib.prf_dotplot_bits_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + window + bits_tail
+        lib.prf_dotplot_counts_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + window + counts_tail
+        lib.prf_dotplot_shape.argtypes = [ctypes.c_uint32] + [ctypes.POINTER(ctypes.c_uint32)] * 3
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
         lib.prf_measure_hbm_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -291,6 +307,55 @@ def _period_call(lib, kmin, kmax, window, length, call):
     return out[:nk * per_k].reshape(nk, per_k), stats
 
 
+def dotplot_shape(min_diagonal_run=3):
+    """(rows per workgroup tile, 64-column words per workgroup span, halo rows) of a dot-plot launch (prf_dotplot_shape; host
+    only; the same for genomes with and without letters outside ACGTN): tile and span boundaries of a window lie at multiples of these from its first row and column."""
+    lib = load_library()
+    out = [ctypes.c_uint32(0) for _ in range(3)]
+    _check(lib, lib.prf_dotplot_shape(min_diagonal_run, *[ctypes.byref(v) for v in out]))
+    return tuple(v.value for v in out)
+
+
+def unpack_bits(bits, n_columns):
+    """uint8[rows, n_columns] of 0 / 1 from packed rows (bit j of word w = column 64 w + j): dotplot_bits, period_bits."""
+    import numpy as np
+    bits = np.ascontiguousarray(bits, dtype="<u8")
+    rows = bits.shape[0]
+    if rows == 0 or n_columns == 0:
+        return np.zeros((rows, n_columns), dtype=np.uint8)
+    return np.unpackbits(bits.view(np.uint8).reshape(rows, -1), axis=1, bitorder="little")[:, :n_columns]
+
+
+def _dot_window(length, rows, cols, min_diagonal_run, block):
+    """((row0, row1, col0, col1) as given to the library, (rows, columns) of the clipped window) after the binding's checks."""
+    if isinstance(min_diagonal_run, bool) or not 0 <= operator.index(min_diagonal_run) <= 0xFFFFFFFF:
+        raise ValueError(f"min_diagonal_run is set to {min_diagonal_run}. It must be at least 0.")
+    if block is not None and (block < 64 or block % 64 or block > 32768):
+        raise ValueError(f"block is {block}. It must be a multiple of 64, at least 64 and at most 32768.")
+    out = []
+    for name, pair in (("rows", rows), ("cols", cols)):
+        lo, hi = (0, None) if pair is None else pair
+        if lo < 0 or (hi is not None and lo > hi):
+            raise ValueError(f"{name} {lo} .. {hi}: an empty range is given as lo == hi")
+        out.append((lo, END_OF_CONTIG if hi is None else hi))
+    clipped = [max(0, min(hi, length) - min(lo, length)) for lo, hi in out]
+    return (out[0][0], out[0][1], out[1][0], out[1][1]), tuple(clipped)
+
+
+def _dot_call(lib, shape, block, call):
+    """The output array of a dot-plot call on a clipped window of shape (rows, columns), filled by call(dst, capacity, n0, n1,
+    stats): uint64[rows, words] for block None, uint32[block rows, block columns] otherwise.  Returns (array, stats)."""
+    import numpy as np
+    unit = 64 if block is None else block
+    n_rows = shape[0] if block is None else -(-shape[0] // unit)
+    n_cols = -(-shape[1] // unit)
+    out = np.zeros(max(1, n_rows * n_cols), dtype=np.uint64 if block is None else np.uint32)
+    n0, n1, stats = ctypes.c_uint64(0), ctypes.c_uint64(0), ScanStats()
+    _check(lib, call(out.ctypes.data_as(ctypes.c_void_p), n_rows * n_cols, ctypes.byref(n0), ctypes.byref(n1), ctypes.byref(stats)))
+    assert (n0.value == n_cols) if block is None else (n0.value, n1.value) == (n_rows, n_cols), (n0.value, n1.value, n_rows, n_cols)
+    return out[:n_rows * n_cols].reshape(n_rows, n_cols), stats
+
+
 class Genome:
     """Contigs packed and resident in HBM (prf_genome)."""
 
@@ -326,6 +391,36 @@ class Genome:
         """The periodicity matrix itself (prf_period_bits): numpy uint64[kmax - kmin + 1, ceil(length / 64)]; bit j of word w of
         row k - kmin = seq[i] == seq[i + k] for i = begin + 64 w + j, i + k < end."""
         return self._period(contig, kmin, kmax, None, begin, end, with_stats)
+
+    def _dotplot(self, contig, min_diagonal_run, block, begin, end, rows, cols, with_stats, launch_cells):
+        if self.lens is None or not 0 <= contig < len(self.lens):
+            raise ValueError(f"contig {contig}: the genome holds {self.n_contigs}")
+        stop = self.lens[contig] if end is None else min(end, self.lens[contig])
+        if begin < 0 or begin > (stop if end is None else end):
+            raise ValueError(f"begin {begin} is behind end {stop if end is None else end}")
+        win, shape = _dot_window(max(0, stop - begin), rows, cols, min_diagonal_run, block)
+        lib, c_end = self.ctx.lib, END_OF_CONTIG if end is None else end
+        head = (self.ctx._h, self._h, contig, begin, c_end) + win + (min_diagonal_run,)
+        if block is None:
+            call = lambda dst, cap, n0, n1, st: lib.prf_dotplot_bits_ex(*head, dst, cap, n0, st, launch_cells)
+        else:
+            call = lambda dst, cap, n0, n1, st: lib.prf_dotplot_counts_ex(*head, block, dst, cap, n0, n1, st, launch_cells)
+        out, stats = _dot_call(lib, shape, block, call)
+        return (out, stats) if with_stats else out
+
+    def dotplot_bits(self, contig, min_diagonal_run=3, begin=0, end=None, rows=None, cols=None, with_stats=False, launch_cells=0):
+        """The exact dot plot of positions [begin, end) of a contig (prf_dotplot_bits): numpy uint64[rows, ceil(columns / 64)] for
+        the window rows = (row0, row1) x cols = (col0, col1), relative to begin (None: all); bit j of word w of row r = kept(row0
+        + r, col0 + 64 w + j): s[i] == s[j] (N == N matches) on a diagonal or anti-diagonal run of the whole matrix that the
+        reference's filter_out_noise(min_diagonal_run) keeps.  unpack_bits() gives one byte per cell.  launch_cells: cells per
+        launch (0: DOT_LAUNCH_CELLS)."""
+        return self._dotplot(contig, min_diagonal_run, None, begin, end, rows, cols, with_stats, launch_cells)
+
+    def dotplot_counts(self, contig, block, min_diagonal_run=3, begin=0, end=None, rows=None, cols=None, with_stats=False,
+                       launch_cells=0):
+        """Kept cells per block of block x block cells of the window (prf_dotplot_counts): numpy uint32[ceil(rows / block),
+        ceil(columns / block)].  block: a multiple of 64, 64 .. 32768."""
+        return self._dotplot(contig, min_diagonal_run, block, begin, end, rows, cols, with_stats, launch_cells)
 
     @property
     def positions(self):
@@ -514,6 +609,31 @@ class Context:
             call = lambda dst, cap, n, st: lib.prf_period_counts_seq(self._h, arr, begin, c_end, kmin, kmax, window, dst, cap, n, st)
         out, stats = _period_call(lib, kmin, kmax, window, max(0, stop - begin), call)
         return (out, stats) if with_stats else out
+
+    def _dotplot_seq(self, seq, min_diagonal_run, block, begin, end, rows, cols, with_stats):
+        if isinstance(seq, str):
+            seq = seq.encode("ascii", "replace")
+        arr, _keep = _contig_array([seq])
+        stop = len(seq) if end is None else min(end, len(seq))
+        if begin < 0 or begin > (stop if end is None else end):
+            raise ValueError(f"begin {begin} is behind end {stop if end is None else end}")
+        win, shape = _dot_window(max(0, stop - begin), rows, cols, min_diagonal_run, block)
+        lib, c_end = self.lib, END_OF_CONTIG if end is None else end
+        head = (self._h, arr, begin, c_end) + win + (min_diagonal_run,)
+        if block is None:
+            call = lambda dst, cap, n0, n1, st: lib.prf_dotplot_bits_seq(*head, dst, cap, n0, st)
+        else:
+            call = lambda dst, cap, n0, n1, st: lib.prf_dotplot_counts_seq(*head, block, dst, cap, n0, n1, st)
+        out, stats = _dot_call(lib, shape, block, call)
+        return (out, stats) if with_stats else out
+
+    def dotplot_bits(self, seq, min_diagonal_run=3, begin=0, end=None, rows=None, cols=None, with_stats=False):
+        """Genome.dotplot_bits for one sequence (str or bytes) in one call: load, compute, free (prf_dotplot_bits_seq)."""
+        return self._dotplot_seq(seq, min_diagonal_run, None, begin, end, rows, cols, with_stats)
+
+    def dotplot_counts(self, seq, block, min_diagonal_run=3, begin=0, end=None, rows=None, cols=None, with_stats=False):
+        """Genome.dotplot_counts for one sequence (str or bytes) in one call (prf_dotplot_counts_seq)."""
+        return self._dotplot_seq(seq, min_diagonal_run, block, begin, end, rows, cols, with_stats)
 
     def period_counts(self, seq, kmin, kmax, window, begin=0, end=None, with_stats=False):
         """Genome.period_counts for one sequence (str or bytes) in one call: load, count, free (prf_period_counts_seq)."""
