@@ -891,23 +891,15 @@ static int literal_one(prf_ctx *c, const prf_contig &ct, u32 contig_index, u32 k
 // what the literal lane refuses on a context: a row sink, pipelined scans in flight
 static int literal_preamble(const prf_ctx *c, const char *api) {
     if (c->sink) return fail(PRF_EUNSUPPORTED, "min_repeats == 1: not with a row sink (the rows of the literal lane are handed over on the host)");
-    if (c->slot[0].seq || c->slot[1].seq) return fail(PRF_EINVAL, "%s: pipelined scans are in flight on this context", api);
-    return PRF_OK;
+    return refuse_in_flight(c, api);
 }
 
 static int literal_finish(prf_ctx *c, std::vector<prf_hit> &rows, float ms, u32 launches, u64 positions, prf_hits *out,
                           prf_scan_stats *stats) {
     c->last.nhits = 0;  // the rows of this lane live on the host only
     c->last.rows = nullptr;
-    if (stats) {
-        memset(stats, 0, sizeof *stats);
-        stats->scan_ms = stats->phase1_ms = ms;
-        stats->positions = positions;
-        stats->packed_bytes = positions;  // this lane reads the bytes themselves
-        stats->n_candidates = stats->n_hits = rows.size();
-        stats->n_launches = launches;
-        stats->path = 2;
-    }
+    lane_stats(stats, 2, ms, positions, positions, launches);  // packed_bytes: this lane reads the bytes themselves
+    if (stats) stats->n_candidates = stats->n_hits = rows.size();
     if (!out || rows.empty()) return PRF_OK;
     prf_hit *r = (prf_hit *)malloc(rows.size() * sizeof(prf_hit));
     if (!r) return fail(PRF_ENOMEM, "prf_scan_literal: cannot allocate %zu rows", rows.size());

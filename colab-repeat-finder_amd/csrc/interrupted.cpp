@@ -135,7 +135,7 @@ int check_args(const prf_ctx *c, const prf_contig *contigs, int n_contigs, const
         if (contigs[i].len && !contigs[i].ascii) return fail(PRF_EINVAL, "prf_scan_interrupted: NULL sequence");
         if (contigs[i].len >= (1ull << 40)) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: input too large (2^40 positions)");
     }
-    if (c->slot[0].seq || c->slot[1].seq) return fail(PRF_EINVAL, "prf_scan_interrupted: pipelined scans are in flight on this context");
+    if (const int busy = refuse_in_flight(c, "prf_scan_interrupted")) return busy;
     if ((u64)n_contigs * p.nk() > 0x7fffffffull) return fail(PRF_EUNSUPPORTED, "prf_scan_interrupted: too many (sequence, motif size) lanes");
     return PRF_OK;
 }

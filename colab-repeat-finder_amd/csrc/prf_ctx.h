@@ -1,8 +1,10 @@
-// prf_ctx.h -- what the host translation units of libprf that talk to the device (api.cpp, interrupted.cpp) share and nobody
-// else sees: the context, error reporting, the C-boundary guard, parameter checks, a scoped device array.
+// prf_ctx.h -- what the host translation units of libprf that talk to the device (api.cpp, interrupted.cpp, periodicity_host.cpp,
+// dotplot_host.cpp) share and nobody else sees: the context, error reporting, the C-boundary guard, parameter checks, a scoped
+// device array, the refusal while pipelined scans are in flight, the stats of a lane that waits for its own kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <new>
 
 #include "../../include/prf.h"
@@ -126,3 +128,20 @@ struct prf_ctx {
     u64 *stamps_buf = nullptr;      // diagnostic (PRF_STAMPS) builds only
     u32 stamps_n = 0;
 };
+
+// What every lane that uses the stream synchronously refuses: a pipelined scan holds a slot until prf_scan_wait.  `name` is the entry point.
+static int refuse_in_flight(const prf_ctx *c, const char *name) {
+    if (c->slot[0].seq || c->slot[1].seq) return fail(PRF_EINVAL, "%s: pipelined scans are in flight on this context", name);
+    return PRF_OK;
+}
+
+// The stats of a lane that waits for its own kernels (`stats` may be NULL): one phase, no candidates or rows unless the caller adds them
+static void lane_stats(prf_scan_stats *stats, u32 path, float ms, u64 positions, u64 packed_bytes, u32 launches) {
+    if (!stats) return;
+    memset(stats, 0, sizeof *stats);
+    stats->scan_ms = stats->phase1_ms = ms;
+    stats->positions = positions;
+    stats->packed_bytes = packed_bytes;
+    stats->n_launches = launches;
+    stats->path = path;
+}

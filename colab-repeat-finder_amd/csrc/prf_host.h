@@ -1,5 +1,5 @@
 // prf_host.h -- launch wrappers shared between the kernel translation units and the host ones that call them (api.cpp,
-// interrupted.cpp).
+// interrupted.cpp, periodicity_host.cpp, dotplot_host.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -293,18 +293,24 @@ def _period_check(kmin, kmax, window):
         raise ValueError(f"window is {window}. It must be a multiple of 64, at least 64.")
 
 
-def _period_call(lib, kmin, kmax, window, length, call):
-    """The output array of a periodicity call on `length` positions (after clipping), filled by call(dst, capacity, n_out,
-    stats): uint32[nk, windows] for a window, uint64[nk, words] for window None.  Returns (array, stats)."""
+def _clip(begin, end, length):
+    """(positions of [begin, end) of a sequence of `length` positions, `end` as the library takes it).  end None: the length."""
+    stop = length if end is None else min(end, length)
+    if begin < 0 or begin > (stop if end is None else end):
+        raise ValueError(f"begin {begin} is behind end {stop if end is None else end}")
+    return max(0, stop - begin), END_OF_CONTIG if end is None else end
+
+
+def _matrix_call(lib, shape, dtype, n_sizes, call):
+    """The output array dtype[shape] of a periodicity or dot-plot call, filled by call(dst, capacity, *size pointers, stats); the
+    n_sizes size words the library publishes are the last n_sizes entries of shape.  Returns (array, stats)."""
     import numpy as np
-    nk = kmax - kmin + 1
-    unit = 64 if window is None else window
-    per_k = -(-length // unit)
-    out = np.zeros(max(1, nk * per_k), dtype=np.uint64 if window is None else np.uint32)
-    n_out, stats = ctypes.c_uint64(0), ScanStats()
-    _check(lib, call(out.ctypes.data_as(ctypes.c_void_p), nk * per_k, ctypes.byref(n_out), ctypes.byref(stats)))
-    assert n_out.value == per_k, (n_out.value, per_k)
-    return out[:nk * per_k].reshape(nk, per_k), stats
+    total = shape[0] * shape[1]
+    out = np.zeros(max(1, total), dtype=dtype)
+    sizes, stats = [ctypes.c_uint64(0) for _ in range(n_sizes)], ScanStats()
+    _check(lib, call(out.ctypes.data_as(ctypes.c_void_p), total, *[ctypes.byref(n) for n in sizes], ctypes.byref(stats)))
+    assert tuple(n.value for n in sizes) == shape[-n_sizes:], ([n.value for n in sizes], shape)
+    return out[:total].reshape(shape), stats
 
 
 def dotplot_shape(min_diagonal_run=3):
@@ -342,18 +348,41 @@ def _dot_window(length, rows, cols, min_diagonal_run, block):
     return (out[0][0], out[0][1], out[1][0], out[1][1]), tuple(clipped)
 
 
-def _dot_call(lib, shape, block, call):
-    """The output array of a dot-plot call on a clipped window of shape (rows, columns), filled by call(dst, capacity, n0, n1,
-    stats): uint64[rows, words] for block None, uint32[block rows, block columns] otherwise.  Returns (array, stats)."""
+def _matrix(ctx, target, begin, end, with_stats, period=None, dot=None):
+    """The one path of the periodicity and dot-plot calls.  target: (genome, contig), or one sequence (str or bytes) for the
+    one-shot _seq entry points.  period: (kmin, kmax, window); dot: (min_diagonal_run, block, rows, cols, launch_cells); window
+    or block None: the bits.  Returns the array, or (array, ScanStats) with_stats."""
     import numpy as np
-    unit = 64 if block is None else block
-    n_rows = shape[0] if block is None else -(-shape[0] // unit)
-    n_cols = -(-shape[1] // unit)
-    out = np.zeros(max(1, n_rows * n_cols), dtype=np.uint64 if block is None else np.uint32)
-    n0, n1, stats = ctypes.c_uint64(0), ctypes.c_uint64(0), ScanStats()
-    _check(lib, call(out.ctypes.data_as(ctypes.c_void_p), n_rows * n_cols, ctypes.byref(n0), ctypes.byref(n1), ctypes.byref(stats)))
-    assert (n0.value == n_cols) if block is None else (n0.value, n1.value) == (n_rows, n_cols), (n0.value, n1.value, n_rows, n_cols)
-    return out[:n_rows * n_cols].reshape(n_rows, n_cols), stats
+    if period is not None:
+        _period_check(*period)
+    if isinstance(target, tuple):
+        genome, contig = target
+        if genome.lens is None or not 0 <= contig < len(genome.lens):
+            raise ValueError(f"contig {contig}: the genome holds {genome.n_contigs}")
+        where, length, form = (genome._h, contig), genome.lens[contig], ""
+    else:
+        seq = target.encode("ascii", "replace") if isinstance(target, str) else target
+        arr, _keep = _contig_array([seq])
+        where, length, form = (arr,), len(seq), "_seq"
+    n, c_end = _clip(begin, end, length)
+    tail = ()
+    if period is not None:
+        kmin, kmax, unit = period
+        product, args = "period", (begin, c_end, kmin, kmax)
+        shape, n_sizes = (kmax - kmin + 1, -(-n // (64 if unit is None else unit))), 1
+    else:
+        t, unit, rows, cols, launch_cells = dot
+        win, (n_rows, n_cols) = _dot_window(n, rows, cols, t, unit)
+        product, args = "dotplot", (begin, c_end) + win + (t,)
+        if not form:                                      # on a genome: the _ex forms, which take launch_cells
+            form, tail = "_ex", (launch_cells,)
+        shape, n_sizes = ((n_rows, -(-n_cols // 64)), 1) if unit is None else ((-(-n_rows // unit), -(-n_cols // unit)), 2)
+    if unit is not None:
+        args += (unit,)
+    fn = getattr(ctx.lib, f"prf_{product}_{'bits' if unit is None else 'counts'}{form}")
+    out, stats = _matrix_call(ctx.lib, shape, np.uint64 if unit is None else np.uint32, n_sizes,
+                              lambda *out_args: fn(ctx._h, *where, *args, *out_args, *tail))
+    return (out, stats) if with_stats else out
 
 
 class Genome:
@@ -365,48 +394,16 @@ class Genome:
         self.n_contigs = n_contigs
         self.lens = None if lens is None else [int(n) for n in lens]   # contig lengths (period_counts / period_bits clip by them)
 
-    def _period(self, contig, kmin, kmax, window, begin, end, with_stats):
-        _period_check(kmin, kmax, window)
-        if self.lens is None or not 0 <= contig < len(self.lens):
-            raise ValueError(f"contig {contig}: the genome holds {self.n_contigs}")
-        stop = self.lens[contig] if end is None else min(end, self.lens[contig])
-        if begin < 0 or begin > (stop if end is None else end):
-            raise ValueError(f"begin {begin} is behind end {stop if end is None else end}")
-        lib, c_end = self.ctx.lib, END_OF_CONTIG if end is None else end
-        if window is None:
-            call = lambda dst, cap, n, st: lib.prf_period_bits(self.ctx._h, self._h, contig, begin, c_end, kmin, kmax, dst, cap, n, st)
-        else:
-            call = lambda dst, cap, n, st: lib.prf_period_counts(self.ctx._h, self._h, contig, begin, c_end, kmin, kmax, window,
-                                                                 dst, cap, n, st)
-        out, stats = _period_call(lib, kmin, kmax, window, max(0, stop - begin), call)
-        return (out, stats) if with_stats else out
-
     def period_counts(self, contig, kmin, kmax, window, begin=0, end=None, with_stats=False):
         """The periodicity profile of positions [begin, end) of a contig (prf_period_counts): numpy uint32[kmax - kmin + 1,
         ceil(length / window)]; entry (k - kmin, w) = the positions i of window w with seq[i] == seq[i + k], i + k < end (N == N
         matches).  window: a multiple of 64.  end None or beyond the contig: its length.  with_stats: (array, ScanStats)."""
-        return self._period(contig, kmin, kmax, window, begin, end, with_stats)
+        return _matrix(self.ctx, (self, contig), begin, end, with_stats, period=(kmin, kmax, window))
 
     def period_bits(self, contig, kmin, kmax, begin=0, end=None, with_stats=False):
         """The periodicity matrix itself (prf_period_bits): numpy uint64[kmax - kmin + 1, ceil(length / 64)]; bit j of word w of
         row k - kmin = seq[i] == seq[i + k] for i = begin + 64 w + j, i + k < end."""
-        return self._period(contig, kmin, kmax, None, begin, end, with_stats)
-
-    def _dotplot(self, contig, min_diagonal_run, block, begin, end, rows, cols, with_stats, launch_cells):
-        if self.lens is None or not 0 <= contig < len(self.lens):
-            raise ValueError(f"contig {contig}: the genome holds {self.n_contigs}")
-        stop = self.lens[contig] if end is None else min(end, self.lens[contig])
-        if begin < 0 or begin > (stop if end is None else end):
-            raise ValueError(f"begin {begin} is behind end {stop if end is None else end}")
-        win, shape = _dot_window(max(0, stop - begin), rows, cols, min_diagonal_run, block)
-        lib, c_end = self.ctx.lib, END_OF_CONTIG if end is None else end
-        head = (self.ctx._h, self._h, contig, begin, c_end) + win + (min_diagonal_run,)
-        if block is None:
-            call = lambda dst, cap, n0, n1, st: lib.prf_dotplot_bits_ex(*head, dst, cap, n0, st, launch_cells)
-        else:
-            call = lambda dst, cap, n0, n1, st: lib.prf_dotplot_counts_ex(*head, block, dst, cap, n0, n1, st, launch_cells)
-        out, stats = _dot_call(lib, shape, block, call)
-        return (out, stats) if with_stats else out
+        return _matrix(self.ctx, (self, contig), begin, end, with_stats, period=(kmin, kmax, None))
 
     def dotplot_bits(self, contig, min_diagonal_run=3, begin=0, end=None, rows=None, cols=None, with_stats=False, launch_cells=0):
         """The exact dot plot of positions [begin, end) of a contig (prf_dotplot_bits): numpy uint64[rows, ceil(columns / 64)] for
@@ -414,13 +411,13 @@ class Genome:
         + r, col0 + 64 w + j): s[i] == s[j] (N == N matches) on a diagonal or anti-diagonal run of the whole matrix that the
         reference's filter_out_noise(min_diagonal_run) keeps.  unpack_bits() gives one byte per cell.  launch_cells: cells per
         launch (0: DOT_LAUNCH_CELLS)."""
-        return self._dotplot(contig, min_diagonal_run, None, begin, end, rows, cols, with_stats, launch_cells)
+        return _matrix(self.ctx, (self, contig), begin, end, with_stats, dot=(min_diagonal_run, None, rows, cols, launch_cells))
 
     def dotplot_counts(self, contig, block, min_diagonal_run=3, begin=0, end=None, rows=None, cols=None, with_stats=False,
                        launch_cells=0):
         """Kept cells per block of block x block cells of the window (prf_dotplot_counts): numpy uint32[ceil(rows / block),
         ceil(columns / block)].  block: a multiple of 64, 64 .. 32768."""
-        return self._dotplot(contig, min_diagonal_run, block, begin, end, rows, cols, with_stats, launch_cells)
+        return _matrix(self.ctx, (self, contig), begin, end, with_stats, dot=(min_diagonal_run, block, rows, cols, launch_cells))
 
     @property
     def positions(self):
@@ -594,54 +591,21 @@ class Context:
             return rows, stats, out
         return rows, stats
 
-    def _period_seq(self, seq, kmin, kmax, window, begin, end, with_stats):
-        _period_check(kmin, kmax, window)
-        if isinstance(seq, str):
-            seq = seq.encode("ascii", "replace")
-        arr, _keep = _contig_array([seq])
-        stop = len(seq) if end is None else min(end, len(seq))
-        if begin < 0 or begin > (stop if end is None else end):
-            raise ValueError(f"begin {begin} is behind end {stop if end is None else end}")
-        lib, c_end = self.lib, END_OF_CONTIG if end is None else end
-        if window is None:
-            call = lambda dst, cap, n, st: lib.prf_period_bits_seq(self._h, arr, begin, c_end, kmin, kmax, dst, cap, n, st)
-        else:
-            call = lambda dst, cap, n, st: lib.prf_period_counts_seq(self._h, arr, begin, c_end, kmin, kmax, window, dst, cap, n, st)
-        out, stats = _period_call(lib, kmin, kmax, window, max(0, stop - begin), call)
-        return (out, stats) if with_stats else out
-
-    def _dotplot_seq(self, seq, min_diagonal_run, block, begin, end, rows, cols, with_stats):
-        if isinstance(seq, str):
-            seq = seq.encode("ascii", "replace")
-        arr, _keep = _contig_array([seq])
-        stop = len(seq) if end is None else min(end, len(seq))
-        if begin < 0 or begin > (stop if end is None else end):
-            raise ValueError(f"begin {begin} is behind end {stop if end is None else end}")
-        win, shape = _dot_window(max(0, stop - begin), rows, cols, min_diagonal_run, block)
-        lib, c_end = self.lib, END_OF_CONTIG if end is None else end
-        head = (self._h, arr, begin, c_end) + win + (min_diagonal_run,)
-        if block is None:
-            call = lambda dst, cap, n0, n1, st: lib.prf_dotplot_bits_seq(*head, dst, cap, n0, st)
-        else:
-            call = lambda dst, cap, n0, n1, st: lib.prf_dotplot_counts_seq(*head, block, dst, cap, n0, n1, st)
-        out, stats = _dot_call(lib, shape, block, call)
-        return (out, stats) if with_stats else out
-
     def dotplot_bits(self, seq, min_diagonal_run=3, begin=0, end=None, rows=None, cols=None, with_stats=False):
         """Genome.dotplot_bits for one sequence (str or bytes) in one call: load, compute, free (prf_dotplot_bits_seq)."""
-        return self._dotplot_seq(seq, min_diagonal_run, None, begin, end, rows, cols, with_stats)
+        return _matrix(self, seq, begin, end, with_stats, dot=(min_diagonal_run, None, rows, cols, 0))
 
     def dotplot_counts(self, seq, block, min_diagonal_run=3, begin=0, end=None, rows=None, cols=None, with_stats=False):
         """Genome.dotplot_counts for one sequence (str or bytes) in one call (prf_dotplot_counts_seq)."""
-        return self._dotplot_seq(seq, min_diagonal_run, block, begin, end, rows, cols, with_stats)
+        return _matrix(self, seq, begin, end, with_stats, dot=(min_diagonal_run, block, rows, cols, 0))
 
     def period_counts(self, seq, kmin, kmax, window, begin=0, end=None, with_stats=False):
         """Genome.period_counts for one sequence (str or bytes) in one call: load, count, free (prf_period_counts_seq)."""
-        return self._period_seq(seq, kmin, kmax, window, begin, end, with_stats)
+        return _matrix(self, seq, begin, end, with_stats, period=(kmin, kmax, window))
 
     def period_bits(self, seq, kmin, kmax, begin=0, end=None, with_stats=False):
         """Genome.period_bits for one sequence (str or bytes) in one call (prf_period_bits_seq)."""
-        return self._period_seq(seq, kmin, kmax, None, begin, end, with_stats)
+        return _matrix(self, seq, begin, end, with_stats, period=(kmin, kmax, None))
 
     def scan_literal(self, seq, kmin, kmax, min_repeats, min_span, stop=None):
         """The literal lane on one sequence (prf_scan_literal); stop: lock-step iterations performed, default all."""

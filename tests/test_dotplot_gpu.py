@@ -256,6 +256,46 @@ def test_scans_and_period_counts_are_not_disturbed(ctx):
         g.free()
 
 
+def test_matrix_calls_wait_for_pipelined_scans_and_fill_their_stats(ctx):
+    """What the two matrix products share on the host: all four calls are refused, under their own names, while a pipelined
+    scan holds a slot (until scan_wait, whether or not its kernel has finished), leave that scan alone, serve afterwards, and
+    fill the stats of a lane that waits for its own kernels."""
+    import prf_native
+    import periodicity_model as P
+    seq = _random(4096, 21)
+    g = ctx.load([seq], 64)                                                   # one launched tile
+    win = dict(rows=(0, 64), cols=(0, 64))
+    calls = [("prf_period_bits", lambda: g.period_bits(0, 1, 4)),
+             ("prf_period_counts", lambda: g.period_counts(0, 1, 4, 64)),
+             ("prf_dotplot_bits", lambda: g.dotplot_bits(0, **win)),
+             ("prf_dotplot_counts", lambda: g.dotplot_counts(0, 64, **win))]
+    try:
+        _, sync = g.scan(1, 6, 3, 9)                                          # sizes the buffers
+        pending = g.scan_async(1, 6, 3, 9)
+        try:
+            for name, call in calls:
+                with pytest.raises(prf_native.PrfError) as info:
+                    call()
+                assert info.value.code == prf_native.PRF_EINVAL, name
+                assert "pipelined scans are in flight" in info.value.message and f"{name}:" in info.value.message
+        finally:
+            waited = ctx.scan_wait(pending)
+        assert waited.n_hits == sync.n_hits
+        got = [call() for _, call in calls]
+        cells = D.kept_cells(seq, 3, 0, None, (0, 64), (0, 64))
+        want = [P.period_bits(seq, 1, 4), P.period_counts(seq, 1, 4, 64), D.pack_bits(cells), D.block_sums(cells, 64)]
+        for (name, _), a, b in zip(calls, got, want):
+            assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), name
+        _, st = g.period_bits(0, 1, 4, with_stats=True)
+        assert (st.path, st.n_launches, st.n_hits, st.positions, st.packed_bytes) == (4, 1, 0, 4096, 1024)
+        empty, st = g.period_bits(0, 1, 4, begin=100, end=100, with_stats=True)
+        assert empty.shape == (4, 0) and st.n_launches == 0 and st.scan_ms == 0 and st.path == 4
+        _, st = g.dotplot_bits(0, with_stats=True, **win)
+        assert (st.path, st.n_launches, st.packed_bytes) == (5, 1, 1024)
+    finally:
+        g.free()
+
+
 def test_cli_writes_plots_density_and_counts(ctx, tmp_path, capsys):
     import plot_dot_plot as cli
     from PIL import Image
