@@ -2,6 +2,8 @@
 // forms; kernel: dotplot.hip).  The path itself is matrix_host.h.  One call = one window of the n x n matrix of a
 // range: the window's rows are cut into launches of at most launch_cells cells (whole tiles of rows; by default fewer cells the
 // larger the threshold, as the filter's cost per cell grows).
+// NOTE: check_room's window clipping and output sizing and launch's cut into launches are repeated in dotpair_host.cpp (pair_request):
+// a change to either belongs in both.
 #include "matrix_host.h"
 
 namespace {
@@ -24,7 +26,7 @@ struct dot_request {
     };
     bool bits() const { return !counts; }
     u32 load_kmax() const { return 64; }
-    int check_view(const prf_contig_view &) const { return PRF_OK; }
+    int check_view(const char *, const prf_genome *, const prf_contig_view &, room *) const { return PRF_OK; }
     void publish(const room &o) const {
         *n_out0 = bits() ? o.out_cols : o.out_rows;
         if (n_out1) *n_out1 = o.out_cols;

@@ -1,27 +1,22 @@
-// dotplot.hip -- the exact dot plot of a range of a resident genome (reference plot_dot_plot.py: generate_matrix,
-// is_noise, filter_out_noise): raw(i, j) = s[i] == s[j] by plain comparison of symbols -- N == N is a match -- and
-//   kept(i, j) = raw(i, j) and (a run of at least m = t - 1 raw cells along (+1, +1) or along (+1, -1) passes through (i, j)),
-// runs taken in the unfiltered n x n matrix and clipped by its bounds alone; the range clips the matrix (the guard gap behind a
-// contig is N and would match N), so rows and columns outside [0, n) are zero and nothing at or behind `end` is read.
+// dotplot_pair.hip -- the exact dot plot of TWO ranges of a resident genome, on either strand:
+//   raw(i, j) = A[i] == B[j]  (strand 0)   or   A[i] == comp(B[j])  (strand 1),
+// A = na positions from a_g_begin (the rows), B = nb positions from b_g_begin (the columns, in B's forward coordinates on both
+// strands), by plain comparison of symbols as in dotplot.hip; comp swaps A/T, C/G, R/Y, K/M, B/V, D/H and leaves every other
+// letter (N, S, W, ...) alone.  kept(i, j) is the closed form of DESIGN 11.1 on the na x nb rectangle: runs are clipped by the
+// rectangle's bounds alone, so rows outside [0, na) and columns outside [0, nb) are zero and nothing at or behind either
+// range's end is read.
 //
-// One kernel template, two outputs:
-//   DOT_BITS    the kept cells of window rows x columns; bit j of word w of row r = kept(row0 + r, col0 + 64 w + j)
-//   DOT_COUNTS  sums of kept cells over blocks of B x B cells of the window, B = 64 * wpb
-//
-// A workgroup owns a tile of DOT_TILE_ROWS rows x a span of span_words 64-column words of the window.  It stages, ONCE per plane,
-// the column words of the span with one halo word on each side (words outside the range as 0, never read), and the symbol of
-// each of its rows with `halo` = m - 1 rows above and below, as a packed word of plane bits.  Then it writes the RAW cells of
-// (tile rows + 2 halo) x (span + 2) words into LDS: a thread owns a column word, whose planes it keeps in registers, and a
-// row's raw word is a select on that row's symbol -- one compare per 64 cells.  The filter reads LDS only:
-//   kept_main = OR_{a < m} AND_{u < m} raw(i + u - a, j + u - a),
-// where row i + k is funnel-shifted by k bits (prf_fsr over two neighbouring words; |k| <= 62 stays within the halo word), and
-// the anti-diagonal is the same with the opposite shift.  m = 2 (the default t = 3) is a template instance of its own, fully
-// unrolled: three rows, five distinct shifted words.  Larger m is the same double loop, m^2 steps per direction.
-// Counts: popcount per thread over its rows, summed per column word in LDS (integer atomics on LDS), then one thread per block
-// column of the span adds the block's words: a plain store where the workgroup owns the whole block (B = 64: a tile's rows are
-// one block row and a word is one block column), a vector atomicAdd on the zeroed entry otherwise.  Integer sums: the result
-// does not depend on the order.  No floating point anywhere.
-// NOTE: dotplot_pair.hip repeats this file's kernel and its two helpers (the two are kept apart so that a change to one cannot alter the
+// The kernel is prf_dotplot_kernel (dotplot.hip: tile, spans, LDS shape, filter, counts -- read the description there) with
+// four differences, all before the raw cells are written:
+//   the row symbols come from A's positions, a row exists for 0 <= i < na;
+//   the column words are staged from B's positions, zero outside B's words;
+//   the column validity mask is built against nb;
+//   on the minus strand the staged ROW symbol is complemented (A[i] == comp(B[j]) <=> comp(A[i]) == B[j]): with the base code
+//   A=0 C=1 T=2 G=3 that flips the high code bit H of an ACGT row; a row with X set and a letter code goes through
+//   dot_comp_letter; an N row (X alone) stays.  The per-cell loop is the same.
+// The self plot keeps its own translation unit and its own copies of the two helpers, so that its kernels are compiled from
+// the text they were compiled from before.
+// NOTE: dotplot.hip repeats this file's kernel and its two helpers (the two are kept apart so that a change to one cannot alter the
 // instructions of the other's instances).
 // A fix to the staging, the filter or the count section belongs in BOTH files; tests/test_dotpair_gpu.py compares the two
 // kernels bit for bit on a few windows (pair(A, A, +) = the self plot) and nothing else keeps them in step.
@@ -49,8 +44,24 @@ __device__ __forceinline__ u64 dot_shifted(const u64 *raw, u32 cw, u32 row, u32 
     return d >= 0 ? prf_fsr(r[0], r[1], (unsigned)d) : prf_fsr(r[-1], r[0], (unsigned)(64 + d));
 }
 
+// the complement of a letter outside ACGTN by its 5-bit code (A = 1 ... Z = 26; 0: N, which stays): R <-> Y, K <-> M, B <-> V,
+// D <-> H; S, W and every other letter map to themselves
+__device__ __forceinline__ u32 dot_comp_letter(u32 e) {
+    switch (e) {
+        case 18u: return 25u;   // R -> Y
+        case 25u: return 18u;
+        case 11u: return 13u;   // K -> M
+        case 13u: return 11u;
+        case 2u: return 22u;    // B -> V
+        case 22u: return 2u;
+        case 4u: return 8u;     // D -> H
+        case 8u: return 4u;
+        default: return e;
+    }
+}
+
 template <int MODE, bool EXOTIC, int MFIX>
-__global__ __launch_bounds__(DOT_THREADS) void prf_dotplot_kernel(const prf_dotplot_args a) {
+__global__ __launch_bounds__(DOT_THREADS) void prf_dotpair_kernel(const prf_dotpair_args a) {
     extern __shared__ __attribute__((aligned(16))) u64 dot_lds[];
     constexpr int NP = EXOTIC ? 8 : 3;
     const u32 m = MFIX ? (u32)MFIX : a.m;
@@ -67,12 +78,12 @@ __global__ __launch_bounds__(DOT_THREADS) void prf_dotplot_kernel(const prf_dotp
     const u32 c = tid & (cw - 1u), rsub = tid / cw, rstep = DOT_THREADS / cw;
     const u32 sp = blockIdx.x % a.n_spans, ti = blockIdx.x / a.n_spans;
     const u64 span_w0 = (u64)sp * a.span_words;        // first word of the span, in words of the window
-    const u64 tr0 = a.lrow0 + (u64)ti * DOT_TILE_ROWS; // first row of the tile, relative to the range
-    const u64 wfirst = a.g_begin >> 6, wlast = (a.g_begin + a.n - 1) >> 6;   // the words of the planes that hold the range
+    const u64 tr0 = a.lrow0 + (u64)ti * DOT_TILE_ROWS; // first row of the tile, relative to A
+    const u64 wfirst = a.b_g_begin >> 6, wlast = (a.b_g_begin + a.nb - 1) >> 6;   // the words of the planes that hold B
 
-    // ---- stage the column words: LDS word i of a plane = plane word sw0 + i, or 0 outside the range's words
+    // ---- stage the column words: LDS word i of a plane = plane word sw0 + i, or 0 outside B's words
     const long long j0 = (long long)a.col0 + 64ll * ((long long)span_w0 - 1ll);   // column of bit 0 of LDS word 0 (may be < 0)
-    const long long q0 = (long long)a.g_begin + j0;
+    const long long q0 = (long long)a.b_g_begin + j0;
     const long long sw0 = q0 >> 6;
     const u32 s = (u32)(q0 & 63);
     {
@@ -86,18 +97,22 @@ __global__ __launch_bounds__(DOT_THREADS) void prf_dotplot_kernel(const prf_dotp
             }
         }
     }
-    // ---- the symbols of the rows: bit 0 H, 1 L, 2 X, 3..7 E, 8 = the row exists
+    // ---- the symbols of the rows, from A: bit 0 H, 1 L, 2 X, 3..7 E, 8 = the row exists; complemented on the minus strand
     for (u32 r = tid; r < rb; r += DOT_THREADS) {
         const long long i = (long long)tr0 - (long long)halo + (long long)r;
         u32 sym = 0;
-        if (i >= 0 && i < (long long)a.n) {
-            const u64 pos = a.g_begin + (u64)i;
+        if (i >= 0 && i < (long long)a.na) {
+            const u64 pos = a.a_g_begin + (u64)i;
             const u64 w = pos >> 6;
             const u32 b = (u32)(pos & 63);
             sym = 256u | (u32)((a.pl.H[w] >> b) & 1ull) | (u32)((a.pl.L[w] >> b) & 1ull) << 1 | (u32)((a.pl.X[w] >> b) & 1ull) << 2;
             if (EXOTIC) {
 #pragma unroll
                 for (int e = 0; e < 5; e++) sym |= (u32)((a.pl.E[e][w] >> b) & 1ull) << (3 + e);
+            }
+            if (a.strand) {
+                if (!(sym & 4u)) sym ^= 1u;                                    // A <-> T, C <-> G
+                else if (EXOTIC) sym = (sym & ~(31u << 3)) | dot_comp_letter((sym >> 3) & 31u) << 3;
             }
         }
         rowsym[r] = sym;
@@ -108,7 +123,7 @@ __global__ __launch_bounds__(DOT_THREADS) void prf_dotplot_kernel(const prf_dotp
     // ---- raw cells: a thread owns column word c
     {
         const long long jc = j0 + 64ll * (long long)c;                         // column of bit 0 of this word
-        const u64 valid = dot_mask_range(-jc, (long long)a.n - jc);            // columns 0 <= j < n
+        const u64 valid = dot_mask_range(-jc, (long long)a.nb - jc);           // columns 0 <= j < nb
         const u64 ch = prf_fsr(planes[c], planes[c + 1], s);
         const u64 cl = prf_fsr(planes[pstride + c], planes[pstride + c + 1], s);
         const u64 cx = prf_fsr(planes[2 * pstride + c], planes[2 * pstride + c + 1], s);
@@ -185,31 +200,24 @@ __global__ __launch_bounds__(DOT_THREADS) void prf_dotplot_kernel(const prf_dotp
 }
 
 template <int MODE>
-hipError_t dot_launch(hipStream_t st, const prf_dotplot_args &a, dim3 grid, size_t lds) {
+hipError_t pair_launch(hipStream_t st, const prf_dotpair_args &a, dim3 grid, size_t lds) {
     const bool exotic = a.pl.E[0] != nullptr;
     if (a.m == 2u) {
-        if (exotic) hipLaunchKernelGGL((prf_dotplot_kernel<MODE, true, 2>), grid, dim3(DOT_THREADS), lds, st, a);
-        else hipLaunchKernelGGL((prf_dotplot_kernel<MODE, false, 2>), grid, dim3(DOT_THREADS), lds, st, a);
+        if (exotic) hipLaunchKernelGGL((prf_dotpair_kernel<MODE, true, 2>), grid, dim3(DOT_THREADS), lds, st, a);
+        else hipLaunchKernelGGL((prf_dotpair_kernel<MODE, false, 2>), grid, dim3(DOT_THREADS), lds, st, a);
     } else {
-        if (exotic) hipLaunchKernelGGL((prf_dotplot_kernel<MODE, true, 0>), grid, dim3(DOT_THREADS), lds, st, a);
-        else hipLaunchKernelGGL((prf_dotplot_kernel<MODE, false, 0>), grid, dim3(DOT_THREADS), lds, st, a);
+        if (exotic) hipLaunchKernelGGL((prf_dotpair_kernel<MODE, true, 0>), grid, dim3(DOT_THREADS), lds, st, a);
+        else hipLaunchKernelGGL((prf_dotpair_kernel<MODE, false, 0>), grid, dim3(DOT_THREADS), lds, st, a);
     }
     return hipGetLastError();
 }
 
 }  // namespace
 
-// The shape of a launch: the raw rows of a tile (64 + 2 halo) x (span + 2) words and the staged planes (3 or 8: the same shape
-// serves both plane sets) fit 64 KiB of LDS
-void prf_dotplot_shape_for(u32 min_diagonal_run, u32 *tile_rows, u32 *span_words, u32 *halo) {
-    const u32 m = min_diagonal_run > 2u ? min_diagonal_run - 1u : 1u;
-    *halo = m - 1u;
-    *tile_rows = DOT_TILE_ROWS;
-    *span_words = *halo <= 16u ? 62u : 30u;      // up to 96 raw rows of 64 words, or up to 188 of 32: 48 KiB
-}
-
-hipError_t prf_launch_dotplot(hipStream_t st, prf_dotplot_args a, bool want_bits) {
-    if (!a.n || a.lrow1 <= a.lrow0 || a.col1 <= a.col0) return hipSuccess;
+// The launch shape is the self plot's (prf_dotplot_shape_for, dotplot.hip): the same LDS serves both kernels.
+hipError_t prf_launch_dotpair(hipStream_t st, prf_dotpair_args a, bool want_bits) {
+    if (!a.na || !a.nb || a.lrow1 <= a.lrow0 || a.col1 <= a.col0) return hipSuccess;
+    if (a.strand > 1u) return hipErrorInvalidValue;
     const bool exotic = a.pl.E[0] != nullptr;
     prf_dotplot_shape_for(a.m + 1u, &a.tile_rows, &a.span_words, &a.halo);
     const u64 n_spans = (a.words_per_row + a.span_words - 1) / a.span_words;
@@ -219,5 +227,5 @@ hipError_t prf_launch_dotplot(hipStream_t st, prf_dotplot_args a, bool want_bits
     const u32 cw = a.span_words + 2u, rb = DOT_TILE_ROWS + 2u * a.halo;
     const size_t lds = ((size_t)(exotic ? 8 : 3) * (cw + 2u) + (size_t)rb * cw) * sizeof(u64) + (((rb + 1u) & ~1u) + cw) * sizeof(u32);
     const dim3 grid((u32)(n_spans * n_tiles));
-    return want_bits ? dot_launch<DOT_BITS>(st, a, grid, lds) : dot_launch<DOT_COUNTS>(st, a, grid, lds);
+    return want_bits ? pair_launch<DOT_BITS>(st, a, grid, lds) : pair_launch<DOT_COUNTS>(st, a, grid, lds);
 }

@@ -1,6 +1,8 @@
-// matrix_host.h -- the host path that the matrix products share (periodicity_host.cpp, dotplot_host.cpp; nobody else includes it).
+// matrix_host.h -- the host path that the matrix products share (periodicity_host.cpp, dotplot_host.cpp, dotpair_host.cpp; nobody
+// else includes it).
 //
-// One call = one range of one contig of a resident genome: judge the arguments (before the context or the genome is looked at),
+// One call = one range of one contig of a resident genome (a product of two ranges names the second one in its request and
+// resolves it in check_view): judge the arguments (before the context or the genome is looked at),
 // take the contig's planes, clip `end`, size and zero the output on the device, launch between two events, copy the output to the
 // caller.  Nothing of the scans' state is touched: no selection is read, no row sink written, the rows of the last scan stay
 // where they are.  The order of the refusals is part of the interface (tests/test_periodicity_cpu.py, tests/test_dotplot_cpu.py).
@@ -8,10 +10,10 @@
 // A product is its request R:
 //   static constexpr u32 path                      prf_scan_stats.path
 //   u64 begin, end;  bool bits() const             the range; words of bits (no zeroing) or 32-bit counts
-//   struct room { u64 n; u64 total() const; ... }  the clipped range, the entries of the output
+//   struct room { u64 n; u64 total() const; ... }  the positions the call covers (the stats' positions), the entries of the output
 //   int check(name) const                          what can be said without a genome
 //   int check_room(name, seq_len, room *) const    what needs the length of the sequence
-//   int check_view(view) const                     what needs the genome
+//   int check_view(name, genome, view, room *) const   what needs the genome; may note in the room what check_room needs from it
 //   void publish(room) const                       the sizes, to the caller's size pointers
 //   u32 load_kmax() const                          the kmax_hint a one-shot call loads its sequence with
 //   int launch(stream, view, room, d_out, u32 *launches) const
@@ -41,6 +43,14 @@ static int matrix_check_output(const char *name, bool bits, u64 capacity, u64 a,
     return PRF_OK;
 }
 
+// what the packer would refuse, found on the host
+static int matrix_check_letters(const char *name, const prf_contig *seq) {
+    for (u64 i = 0; i < seq->len; i++)
+        if (!isalpha(seq->ascii[i]) || seq->ascii[i] > 127)
+            return fail(PRF_ESYMBOL, "%s: unsupported symbol at position %llu: only letters can be packed", name, (unsigned long long)i);
+    return PRF_OK;
+}
+
 template <class R>
 static int matrix_run(const char *name, prf_ctx *c, const prf_genome *g, u32 contig, const R &r, prf_scan_stats *stats) {
     if (!c) return fail(PRF_EINVAL, "%s: NULL context", name);
@@ -48,8 +58,8 @@ static int matrix_run(const char *name, prf_ctx *c, const prf_genome *g, u32 con
     int rc = prf_genome_contig_view(g, contig, &v);
     if (rc) return rc;
     if (v.ctx != c) return fail(PRF_EINVAL, "%s: the genome belongs to another context", name);
-    if ((rc = r.check_view(v))) return rc;
     typename R::room o;
+    if ((rc = r.check_view(name, g, v, &o))) return rc;
     if ((rc = r.check_room(name, v.len, &o))) return rc;
     if ((rc = refuse_in_flight(c, name))) return rc;
     HIPCHK(hipSetDevice(c->dev));
@@ -89,9 +99,7 @@ static int matrix_one_shot(const char *name, prf_ctx *c, const prf_contig *seq, 
         if (!seq || (seq->len && !seq->ascii)) return fail(PRF_EINVAL, "%s: NULL sequence", name);
         typename R::room o;
         if ((rc = r.check_room(name, seq->len, &o))) return rc;
-        for (u64 i = 0; i < seq->len; i++)
-            if (!isalpha(seq->ascii[i]) || seq->ascii[i] > 127)
-                return fail(PRF_ESYMBOL, "%s: unsupported symbol at position %llu: only letters can be packed", name, (unsigned long long)i);
+        if ((rc = matrix_check_letters(name, seq))) return rc;
         if (!c) return fail(PRF_EINVAL, "%s: NULL context", name);
         prf_genome *g = nullptr;
         if ((rc = prf_genome_load(c, seq, 1, r.load_kmax(), &g))) return rc;

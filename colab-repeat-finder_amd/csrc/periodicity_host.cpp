@@ -19,7 +19,7 @@ struct per_request {
     bool bits() const { return window == 0; }
     u32 load_kmax() const { return kmax; }
     void publish(const room &o) const { *n_out = o.per_k; }
-    int check_view(const prf_contig_view &v) const { return check_params(kmin, kmax, 1, 1, v.kmax_hint); }
+    int check_view(const char *, const prf_genome *, const prf_contig_view &v, room *) const { return check_params(kmin, kmax, 1, 1, v.kmax_hint); }
 
     int check(const char *name) const {
         int rc = check_params(kmin, kmax, 1, 1, 0);

@@ -1,5 +1,5 @@
 // prf_host.h -- launch wrappers shared between the kernel translation units and the host ones that call them (api.cpp,
-// interrupted.cpp, periodicity_host.cpp, dotplot_host.cpp).
+// interrupted.cpp, periodicity_host.cpp, dotplot_host.cpp, dotpair_host.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -164,3 +164,23 @@ struct prf_dotplot_args {
 // rows per workgroup tile, words of 64 columns per workgroup span, halo rows above and below (= m - 1); the same for 3 and 8 planes
 void prf_dotplot_shape_for(u32 min_diagonal_run, u32 *tile_rows, u32 *span_words, u32 *halo);
 hipError_t prf_launch_dotplot(hipStream_t s, prf_dotplot_args a, bool want_bits);
+
+// dot plot of two ranges (dotplot_pair.hip): kept cells of window rows x columns of the na x nb matrix A[i] == B[j]
+// (strand 0) or A[i] == comp(B[j]) (strand 1), A = the na positions from global position a_g_begin, B = the nb from b_g_begin,
+// both of the same planes; nothing at or behind either range's end is compared (or read), runs are judged on the whole rectangle.
+// The fields that prf_dotplot_args has too mean the same.
+struct prf_dotpair_args {
+    prf_planes pl;
+    u64 a_g_begin, na, b_g_begin, nb;
+    u64 row0, col0, col1;
+    u64 lrow0, lrow1;
+    u64 words_per_row;
+    u32 m;
+    u32 wpb;
+    u64 n_block_cols;
+    u64 *bits;
+    u32 *counts;
+    u32 strand;
+    u32 tile_rows, span_words, halo, n_spans;  // set by the launch wrapper (prf_dotplot_shape_for)
+};
+hipError_t prf_launch_dotpair(hipStream_t s, prf_dotpair_args a, bool want_bits);

@@ -7,6 +7,10 @@ The reference's arguments, for sequences of at most 5,000 positions (one pixel p
 Beyond the reference: --block B turns the plot into a density image -- one pixel per block of B x B cells, grey = kept cells /
 cells of the block -- which has no such limit, and --tsv writes the counts:
     plot_dot_plot.py -R genome.fa chr22:20000000-21000000 --block 1024 --tsv density.tsv -o density.png
+Also beyond it: --versus X plots the inputs (rows) against another sequence or interval X (columns), a rectangular image, and
+--strand - compares with the complement of the columns' bases, so that an inverted repeat shows as an anti-diagonal; --strand both
+draws the cells that only the minus strand keeps in a second colour:
+    plot_dot_plot.py -R genome.fa chr22:1000-3000 --versus chr21:5000-6500 --strand both -o pair.png
 """
 import argparse
 import gzip
@@ -35,18 +39,32 @@ def _context(context):
     return prf_native.default_context()
 
 
-def dot_plot_matrix(sequence, min_diagonal_run=3, set_noise_to=0, context=None):
+MINUS_ONLY = 3                 # the value of a cell that only the minus strand keeps (--strand both)
+
+
+def dot_plot_matrix(sequence, min_diagonal_run=3, set_noise_to=0, context=None, versus=None, strand="+"):
     """numpy uint8[n, n]: 1 where the reference's generate_matrix + filter_out_noise(min_diagonal_run) leave a 1, set_noise_to
     where they put set_noise_to, 0 elsewhere -- from the GPU: one call at min_diagonal_run, and one more without a filter if
-    the filtered-out cells are wanted."""
+    the filtered-out cells are wanted.
+    versus: the sequence of the columns (None: `sequence` itself), which makes the matrix uint8[len(sequence), len(versus)].
+    strand "-": a cell compares a row's base with the complement of the column's base; "both": one call per strand, cells that
+    only the minus strand keeps are MINUS_ONLY, filtered-out cells are those that neither strand keeps."""
     import prf_native
-    n = len(sequence)
     ctx = _context(context)
-    kept = prf_native.unpack_bits(ctx.dotplot_bits(sequence, min_diagonal_run), n)
+    columns = sequence if versus is None else versus
+
+    def cells(t):
+        if versus is None and strand == "+":
+            return prf_native.unpack_bits(ctx.dotplot_bits(sequence, t), len(columns))
+        per_strand = [prf_native.unpack_bits(ctx.dotpair_bits(sequence, columns, s, t), len(columns)) for s in "+-" if strand in (s, "both")]
+        return per_strand[0] if len(per_strand) == 1 else per_strand[0] | (per_strand[1] << 1)      # bit 0: plus, bit 1: minus
+
+    kept = cells(min_diagonal_run)
+    out = np.where(kept == 2, MINUS_ONLY, kept & 1).astype(np.uint8) if strand == "both" else kept
     if not set_noise_to or min_diagonal_run <= 2:
-        return kept
-    raw = prf_native.unpack_bits(ctx.dotplot_bits(sequence, 0), n)
-    return (kept + set_noise_to * (raw & ~kept & 1)).astype(np.uint8)
+        return out
+    raw = cells(0)
+    return (out + set_noise_to * ((raw != 0) & (kept == 0))).astype(np.uint8)
 
 
 def generate_matrix(sequence, context=None):
@@ -110,17 +128,22 @@ def filter_out_noise(matrix, min_diagonal_run=3, set_noise_to=0):
             row[j] = set_noise_to
 
 
-PALETTE = ("white", "black", "red")     # cell values 0 (empty), 1 (kept), 2 (filtered out, --show-filtered-pixels)
+# cell values 0 (empty), 1 (kept), 2 (filtered out, --show-filtered-pixels), 3 (kept on the minus strand only, --strand both)
+PALETTE = ("white", "black", "red", "royalblue")
 
 
 def _draw(image, save_path, show, figure_size, **imshow):
-    """One square image without ticks, with a thin grey frame, cropped to the axes when saved."""
+    """One image without ticks, with a thin grey frame, cropped to the axes when saved: figure_size inches along its longer
+    side, the other side in proportion (a square for a square matrix)."""
     import matplotlib
     if not show:
         matplotlib.use("Agg")
     import matplotlib.pyplot as plt
-    fig, ax = plt.subplots(figsize=(figure_size, figure_size))
-    if len(image):
+    n_rows, n_cols = np.shape(image) if np.ndim(image) == 2 else (0, 0)
+    longer = max(n_rows, n_cols, 1)
+    fig, ax = plt.subplots(figsize=(figure_size * max(n_cols, 1) / longer, figure_size * max(n_rows, 1) / longer) if n_rows != n_cols
+                           else (figure_size, figure_size))
+    if n_rows and n_cols:
         ax.imshow(image, interpolation="nearest", **imshow)
     ax.tick_params(left=False, bottom=False, labelleft=False, labelbottom=False)
     for side in ("left", "right", "top", "bottom"):
@@ -133,28 +156,32 @@ def _draw(image, save_path, show, figure_size, **imshow):
 
 
 def plot_dot_plot(matrix, save_path=None, show=False, figure_size=None):
-    """Draw the matrix as a square image: 0 white, 1 black, 2 (filtered-out cells) red.  figure_size (inches) defaults to the
-    reference's 5 * len(matrix) / 150."""
+    """Draw the matrix as an image, square for a square matrix: 0 white, 1 black, 2 (filtered-out cells) red, 3 (cells of the
+    minus strand only) blue.  figure_size (inches, the longer side) defaults to the reference's 5 * len(matrix) / 150."""
     from matplotlib.colors import ListedColormap
-    size = len(matrix)
-    top = int(np.max(matrix)) if size else 0
+    size = max(np.shape(matrix)) if np.ndim(matrix) == 2 else len(matrix)
+    top = int(np.max(matrix)) if np.size(matrix) else 0
     _draw(matrix, save_path, show, max(5 * size / 150, 0.2) if figure_size is None else figure_size,
           cmap=ListedColormap(list(PALETTE[:top + 1])), vmin=0, vmax=top)
 
 
-def plot_density(counts, block, n, save_path=None, show=False, figure_size=None):
-    """Draw block counts (dotplot_counts of an n x n matrix) as a grey image: kept cells / cells of the (clipped) block."""
-    edge = np.minimum(block, n - block * np.arange(counts.shape[0])).astype(np.float64)
-    density = counts / np.outer(edge, edge)
-    _draw(density, save_path, show, min(max(5 * counts.shape[0] / 150, 2.0), 40.0) if figure_size is None else figure_size,
+def plot_density(counts, block, n, save_path=None, show=False, figure_size=None, n_cols=None):
+    """Draw block counts (dotplot_counts of an n x n matrix, or dotpair_counts of an n x n_cols one) as a grey image: kept cells /
+    cells of the (clipped) block."""
+    edges = [np.minimum(block, length - block * np.arange(blocks)).astype(np.float64)
+             for length, blocks in zip((n, n if n_cols is None else n_cols), counts.shape)]
+    density = counts / np.outer(*edges)
+    _draw(density, save_path, show, min(max(5 * max(counts.shape) / 150, 2.0), 40.0) if figure_size is None else figure_size,
           cmap="gray_r", vmin=0.0, vmax=1.0)
 
 
-def density_lines(name, begin, n, block, counts):
-    """The --tsv lines: name, row start, row end, column start, column end, kept cells; one line per block with a kept cell."""
+def density_lines(name, begin, n, block, counts, col_begin=None, n_cols=None):
+    """The --tsv lines: name, row start, row end, column start, column end, kept cells; one line per block with a kept cell.
+    col_begin, n_cols: where the columns begin and how many they are, if not as the rows (--versus)."""
+    col_begin, n_cols = begin if col_begin is None else col_begin, n if n_cols is None else n_cols
     for r, c in zip(*(v.tolist() for v in counts.nonzero())):
-        yield (f"{name}\t{begin + r * block}\t{begin + min(n, (r + 1) * block)}\t{begin + c * block}\t"
-               f"{begin + min(n, (c + 1) * block)}\t{int(counts[r, c])}\n")
+        yield (f"{name}\t{begin + r * block}\t{begin + min(n, (r + 1) * block)}\t{col_begin + c * block}\t"
+               f"{col_begin + min(n_cols, (c + 1) * block)}\t{int(counts[r, c])}\n")
 
 
 def build_parser():
@@ -173,7 +200,14 @@ def build_parser():
     p.add_argument("-v", "--verbose", action="store_true", help="report every sequence as it is plotted")
     p.add_argument("--block", type=int, help="Plot the density instead: one pixel per block of this many x this many cells (a "
                                              "multiple of 64, at most 32768). Needed above 5,000 positions.")
-    p.add_argument("--tsv", help="With --block: also write the block counts as a table.")
+    p.add_argument("--tsv", help="With --block: also write the block counts as a table. With --versus the name and the row "
+                                 "coordinates are the input's, the column coordinates are X's.")
+    p.add_argument("--versus", metavar="X", help="Plot every input (the rows) against X (the columns) instead of against itself: a "
+                                                 "literal ACGT sequence, or an interval chrom:start_0based-end with -R.")
+    p.add_argument("--strand", choices=["+", "-", "both"], default="+",
+                   help="-: compare each row's base with the complement of the column's base, so that an inverted repeat is an "
+                        "anti-diagonal; both: draw the cells that only the minus strand keeps in a second colour (one pixel per "
+                        "cell only: with --block, plot one strand at a time)")
     p.add_argument("input_sequence_or_intervals_or_bed_files", nargs="+",
                    help="any mix of literal ACGT sequences, intervals chrom:start_0based-end, and BED files")
     return p
@@ -200,6 +234,8 @@ def resolve_inputs(args, parser):
         parser.error(f"--block is set to {args.block}. It must be a multiple of 64, at least 64 and at most 32768.")
     if args.tsv and args.block is None:
         parser.error("--tsv writes the block counts: give --block too")
+    if args.block is not None and args.strand == "both":
+        parser.error("--strand both colours single cells: with --block, plot one strand at a time (--strand + and --strand -)")
     inputs = args.input_sequence_or_intervals_or_bed_files
     out, n_intervals, cache = [], 0, {}
     for i, text in enumerate(inputs):
@@ -245,23 +281,63 @@ def resolve_inputs(args, parser):
     return out
 
 
+def resolve_versus(args, parser):
+    """None, or (name, begin, sequence) of --versus: a literal sequence or an interval of --reference-fasta, widened by --padding
+    like the inputs and under the same limit without --block."""
+    text = args.versus
+    if text is None:
+        return None
+    if not set(text) - set("ACGT"):
+        name, begin, seq = "sequence", 0, text
+    else:
+        if not (":" in text and "-" in text):
+            parser.error(f"Error: --versus {text} is not a valid nucleotide sequence or interval")
+        if not args.reference_fasta:
+            parser.error("Error: --reference-fasta is required when --versus is an interval")
+        try:
+            chrom, start, end = parse_interval(text)
+        except ValueError as e:
+            parser.error(f"Error: {e}")
+        begin, end = max(0, start - args.padding), end + args.padding
+        name, seq = _fetch(parser, args.reference_fasta, {}, chrom, begin, end)
+    if args.block is None and len(seq) > MAX_MATRIX_POSITIONS:
+        parser.error(f"The --versus sequence is too long for one pixel per cell ({len(seq):,d} bp > {MAX_MATRIX_POSITIONS:,d}). "
+                     f"Use --block B (a multiple of 64) to plot the density instead.")
+    if not seq.isalpha() and seq:
+        parser.error(f"Error: the sequence of {name} holds characters that are not letters")
+    return name, begin, seq
+
+
+def density_counts(ctx, seq, block, min_diagonal_run, versus=None, strand="+"):
+    """uint32 block counts of seq against itself, or against versus, on one strand: the self plot's call where it serves."""
+    if versus is None and strand == "+":
+        return ctx.dotplot_counts(seq, block, min_diagonal_run)
+    return ctx.dotpair_counts(seq, seq if versus is None else versus, block, strand, min_diagonal_run)
+
+
 def main(argv=None, context=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     todo = resolve_inputs(args, parser)
+    versus = resolve_versus(args, parser)
     os.makedirs(args.output_dir, exist_ok=True)
     for i, (name, begin, seq, path) in enumerate(todo):
         if args.verbose:
             print(f"[{i + 1}/{len(todo)}] {name}: {len(seq):,d} positions")
+        columns = seq if versus is None else versus[2]
         if args.block is None:
-            matrix = dot_plot_matrix(seq, args.filter_threshold, 2 if args.show_filtered_pixels else 0, context=context)
+            matrix = dot_plot_matrix(seq, args.filter_threshold, 2 if args.show_filtered_pixels else 0, context=context,
+                                     versus=None if versus is None else columns, strand=args.strand)
             plot_dot_plot(matrix, save_path=path, show=args.show_plot, figure_size=args.image_size)
         else:
-            counts = _context(context).dotplot_counts(seq, args.block, args.filter_threshold)
-            plot_density(counts, args.block, len(seq), save_path=path, show=args.show_plot, figure_size=args.image_size)
+            counts = density_counts(_context(context), seq, args.block, args.filter_threshold, None if versus is None else columns,
+                                    args.strand)
+            plot_density(counts, args.block, len(seq), save_path=path, show=args.show_plot, figure_size=args.image_size,
+                         n_cols=len(columns))
             if args.tsv:
                 with open(args.tsv, "wt") as f:
-                    f.writelines(density_lines(name, begin, len(seq), args.block, counts))
+                    f.writelines(density_lines(name, begin, len(seq), args.block, counts, begin if versus is None else versus[1],
+                                               len(columns)))
                 print(f"Wrote {args.tsv}")
         if args.verbose or len(todo) == 1:
             print(f"Wrote {path} ({len(seq):,d} positions)")

@@ -119,6 +119,9 @@ PERIOD_EXPORTS = ["prf_period_counts", "prf_period_bits", "prf_period_counts_seq
 # the dot-plot entry points (include/prf_dotplot.h, which prf.h includes)
 DOTPLOT_EXPORTS = ["prf_dotplot_bits", "prf_dotplot_counts", "prf_dotplot_bits_ex", "prf_dotplot_counts_ex", "prf_dotplot_bits_seq",
                    "prf_dotplot_counts_seq", "prf_dotplot_shape"]
+# the entry points of the dot plot of two ranges (include/prf_dotpair.h, which prf.h includes)
+DOTPAIR_EXPORTS = ["prf_dotpair_bits", "prf_dotpair_counts", "prf_dotpair_bits_ex", "prf_dotpair_counts_ex", "prf_dotpair_bits_seq",
+                   "prf_dotpair_counts_seq"]
 DOT_LAUNCH_CELLS = 1 << 36   # PRF_DOT_LAUNCH_CELLS
 DOT_MAX_CELLS = 1 << 42      # PRF_DOT_MAX_CELLS
 DOT_MAX_RUN = 64             # PRF_DOT_MAX_RUN
@@ -218,6 +221,16 @@ def load_library():
         lib.prf_dotplot_bits_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + window + bits_tail
         lib.prf_dotplot_counts_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + window + counts_tail
         lib.prf_dotplot_shape.argtypes = [ctypes.c_uint32] + [ctypes.POINTER(ctypes.c_uint32)] * 3
+        span = [ctypes.c_uint64] * 2                                # begin, end
+        pair_window = [ctypes.c_uint32] + window[2:]                # strand, row0, row1, col0, col1, min_diagonal_run
+        on_genome = [vp, vp, ctypes.c_uint32] + span + [ctypes.c_uint32] + span + pair_window
+        one_shot = [vp, ctypes.POINTER(_Contig)] + span + [ctypes.POINTER(_Contig)] + span + pair_window
+        lib.prf_dotpair_bits.argtypes = on_genome + bits_tail
+        lib.prf_dotpair_counts.argtypes = on_genome + counts_tail
+        lib.prf_dotpair_bits_ex.argtypes = on_genome + bits_tail + [ctypes.c_uint64]
+        lib.prf_dotpair_counts_ex.argtypes = on_genome + counts_tail + [ctypes.c_uint64]
+        lib.prf_dotpair_bits_seq.argtypes = one_shot + bits_tail
+        lib.prf_dotpair_counts_seq.argtypes = one_shot + counts_tail
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
         lib.prf_measure_hbm_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -332,8 +345,9 @@ def unpack_bits(bits, n_columns):
     return np.unpackbits(bits.view(np.uint8).reshape(rows, -1), axis=1, bitorder="little")[:, :n_columns]
 
 
-def _dot_window(length, rows, cols, min_diagonal_run, block):
-    """((row0, row1, col0, col1) as given to the library, (rows, columns) of the clipped window) after the binding's checks."""
+def _dot_window(n_rows, n_cols, rows, cols, min_diagonal_run, block):
+    """((row0, row1, col0, col1) as given to the library, (rows, columns) of the clipped window) after the binding's checks, for a
+    matrix of n_rows x n_cols."""
     if isinstance(min_diagonal_run, bool) or not 0 <= operator.index(min_diagonal_run) <= 0xFFFFFFFF:
         raise ValueError(f"min_diagonal_run is set to {min_diagonal_run}. It must be at least 0.")
     if block is not None and (block < 64 or block % 64 or block > 32768):
@@ -344,36 +358,61 @@ def _dot_window(length, rows, cols, min_diagonal_run, block):
         if lo < 0 or (hi is not None and lo > hi):
             raise ValueError(f"{name} {lo} .. {hi}: an empty range is given as lo == hi")
         out.append((lo, END_OF_CONTIG if hi is None else hi))
-    clipped = [max(0, min(hi, length) - min(lo, length)) for lo, hi in out]
+    clipped = [max(0, min(hi, length) - min(lo, length)) for (lo, hi), length in zip(out, (n_rows, n_cols))]
     return (out[0][0], out[0][1], out[1][0], out[1][1]), tuple(clipped)
 
 
-def _matrix(ctx, target, begin, end, with_stats, period=None, dot=None):
-    """The one path of the periodicity and dot-plot calls.  target: (genome, contig), or one sequence (str or bytes) for the
-    one-shot _seq entry points.  period: (kmin, kmax, window); dot: (min_diagonal_run, block, rows, cols, launch_cells); window
-    or block None: the bits.  Returns the array, or (array, ScanStats) with_stats."""
-    import numpy as np
-    if period is not None:
-        _period_check(*period)
+STRANDS = {"+": 0, "-": 1}     # the strand argument of the dotpair calls
+
+
+def _matrix_range(target, begin, end):
+    """(what the library is given in front of the range, positions of the clipped range, `end` as the library takes it, what must
+    stay alive during the call: None for a genome) for a target that is (genome, contig) or one sequence (str or bytes)."""
     if isinstance(target, tuple):
         genome, contig = target
         if genome.lens is None or not 0 <= contig < len(genome.lens):
             raise ValueError(f"contig {contig}: the genome holds {genome.n_contigs}")
-        where, length, form = (genome._h, contig), genome.lens[contig], ""
+        where, length, keep = (contig,), genome.lens[contig], None
     else:
         seq = target.encode("ascii", "replace") if isinstance(target, str) else target
-        arr, _keep = _contig_array([seq])
-        where, length, form = (arr,), len(seq), "_seq"
+        arr, keep = _contig_array([seq])
+        where, length = (arr,), len(seq)
     n, c_end = _clip(begin, end, length)
-    tail = ()
+    return where, n, c_end, keep
+
+
+def _matrix(ctx, target, begin, end, with_stats, period=None, dot=None, versus=None):
+    """The one path of the periodicity and dot-plot calls.  target: (genome, contig), or one sequence (str or bytes) for the
+    one-shot _seq entry points.  period: (kmin, kmax, window); dot: (min_diagonal_run, block, rows, cols, launch_cells); window
+    or block None: the bits.  versus: (target, begin, end, strand) of the columns' range, which turns the dot plot into the one
+    of two ranges (target of the same kind; a genome must be the same one).  Returns the array, or (array, ScanStats) with_stats."""
+    import numpy as np
+    if period is not None:
+        _period_check(*period)
+    where, n, c_end, keep = _matrix_range(target, begin, end)
+    one_shot = keep is not None
+    form, tail = ("_seq" if one_shot else ""), ()
+    if not one_shot:
+        where = (target[0]._h,) + where
     if period is not None:
         kmin, kmax, unit = period
         product, args = "period", (begin, c_end, kmin, kmax)
         shape, n_sizes = (kmax - kmin + 1, -(-n // (64 if unit is None else unit))), 1
     else:
         t, unit, rows, cols, launch_cells = dot
-        win, (n_rows, n_cols) = _dot_window(n, rows, cols, t, unit)
-        product, args = "dotplot", (begin, c_end) + win + (t,)
+        product, args, n_b = "dotplot", (begin, c_end), n
+        if versus is not None:
+            b_target, b_begin, b_end, strand = versus
+            if strand not in STRANDS:
+                raise ValueError(f"strand is {strand!r}. It must be '+' or '-'.")
+            if one_shot == isinstance(b_target, tuple):
+                raise ValueError("the two ranges must both be sequences or both lie in a genome")
+            if not one_shot and b_target[0] is not target[0]:
+                raise ValueError("the two ranges must lie in the same resident genome")
+            b_where, n_b, b_c_end, _b_keep = _matrix_range(b_target, b_begin, b_end)
+            product, args = "dotpair", args + b_where + (b_begin, b_c_end, STRANDS[strand])
+        win, (n_rows, n_cols) = _dot_window(n, n_b, rows, cols, t, unit)
+        args += win + (t,)
         if not form:                                      # on a genome: the _ex forms, which take launch_cells
             form, tail = "_ex", (launch_cells,)
         shape, n_sizes = ((n_rows, -(-n_cols // 64)), 1) if unit is None else ((-(-n_rows // unit), -(-n_cols // unit)), 2)
@@ -418,6 +457,20 @@ class Genome:
         """Kept cells per block of block x block cells of the window (prf_dotplot_counts): numpy uint32[ceil(rows / block),
         ceil(columns / block)].  block: a multiple of 64, 64 .. 32768."""
         return _matrix(self.ctx, (self, contig), begin, end, with_stats, dot=(min_diagonal_run, block, rows, cols, launch_cells))
+
+    def dotpair_bits(self, a, b, strand="+", min_diagonal_run=3, rows=None, cols=None, with_stats=False, launch_cells=0):
+        """The exact dot plot of two ranges of this genome (prf_dotpair_bits): a = (contig, begin, end) gives the rows, b the
+        columns (end None: the contig's end).  numpy uint64[rows, ceil(columns / 64)] as dotplot_bits; bit = A[i] == B[j] on
+        strand "+", A[i] == complement(B[j]) on strand "-" (columns in B's forward coordinates: an inverted repeat is an
+        anti-diagonal), on a diagonal or anti-diagonal run of the whole na x nb rectangle that min_diagonal_run keeps."""
+        return _matrix(self.ctx, (self, a[0]), a[1], a[2], with_stats, dot=(min_diagonal_run, None, rows, cols, launch_cells),
+                       versus=((self, b[0]), b[1], b[2], strand))
+
+    def dotpair_counts(self, a, b, block, strand="+", min_diagonal_run=3, rows=None, cols=None, with_stats=False, launch_cells=0):
+        """Kept cells per block of block x block cells of the window of dotpair_bits (prf_dotpair_counts): numpy
+        uint32[ceil(rows / block), ceil(columns / block)]."""
+        return _matrix(self.ctx, (self, a[0]), a[1], a[2], with_stats, dot=(min_diagonal_run, block, rows, cols, launch_cells),
+                       versus=((self, b[0]), b[1], b[2], strand))
 
     @property
     def positions(self):
@@ -598,6 +651,19 @@ class Context:
     def dotplot_counts(self, seq, block, min_diagonal_run=3, begin=0, end=None, rows=None, cols=None, with_stats=False):
         """Genome.dotplot_counts for one sequence (str or bytes) in one call (prf_dotplot_counts_seq)."""
         return _matrix(self, seq, begin, end, with_stats, dot=(min_diagonal_run, block, rows, cols, 0))
+
+    def dotpair_bits(self, seq_a, seq_b, strand="+", min_diagonal_run=3, a=(0, None), b=(0, None), rows=None, cols=None,
+                     with_stats=False):
+        """Genome.dotpair_bits for two sequences (str or bytes; rows from seq_a, columns from seq_b) in one call: load, compute,
+        free (prf_dotpair_bits_seq).  a, b: (begin, end) of the range of each sequence."""
+        return _matrix(self, seq_a, a[0], a[1], with_stats, dot=(min_diagonal_run, None, rows, cols, 0),
+                       versus=(seq_b, b[0], b[1], strand))
+
+    def dotpair_counts(self, seq_a, seq_b, block, strand="+", min_diagonal_run=3, a=(0, None), b=(0, None), rows=None, cols=None,
+                       with_stats=False):
+        """Genome.dotpair_counts for two sequences in one call (prf_dotpair_counts_seq)."""
+        return _matrix(self, seq_a, a[0], a[1], with_stats, dot=(min_diagonal_run, block, rows, cols, 0),
+                       versus=(seq_b, b[0], b[1], strand))
 
     def period_counts(self, seq, kmin, kmax, window, begin=0, end=None, with_stats=False):
         """Genome.period_counts for one sequence (str or bytes) in one call: load, count, free (prf_period_counts_seq)."""
