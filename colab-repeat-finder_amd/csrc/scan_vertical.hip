@@ -171,6 +171,7 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
     static_assert(SLOW_CAP * 16 >= 256, "the all-N stream masks lie in the deferred candidates' list");
     static_assert(2 * LW * 8 <= (int)R1_BYTES, "the window of the linear planes must fit the image's region");
     static_assert((2 * LW / 2 + 63) / 64 <= 5 * MAX_WAVES, "window pieces per wave");
+    static_assert(LEAD_OFF == R1_OFF + 2u * (u32)LW * 8u && LEAD_OFF + 2u * LEAD_CAP * 4u <= R1_OFF + R1_BYTES, "the record waves' stream lists lie in R1 behind the window");
     prf_lds_u4 *vimg = (prf_lds_u4 *)(prf_smem + R1_OFF);
     prf_lds_u64 *recs = (prf_lds_u64 *)(prf_smem + RECS_OFF);
     prf_lds_u32 *keys = (prf_lds_u32 *)(prf_smem + KEYS_OFF);

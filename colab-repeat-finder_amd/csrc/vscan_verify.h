@@ -158,6 +158,19 @@ __device__ __forceinline__ u64 xlook64(const u32 *xw, u32 q) {
     const u32 w0 = xword(xw, w), w1 = xword(xw, w + 1), w2 = xword(xw, w + 2);
     return (u64)__builtin_amdgcn_alignbit(w1, w0, sft) | ((u64)__builtin_amdgcn_alignbit(w2, w1, sft) << 32);
 }
+// A 64-position look in two steps, for code that wants several looks in flight at once: raw64 issues the three reads, cut64
+// shifts the words into place.  Between the two, looks_in_flight() names every raw look as an operand of one empty asm
+// statement: left alone the compiler waits for each look before it issues the next (a round trip each).
+typedef u32 prf_u32x3 __attribute__((ext_vector_type(3)));
+__device__ __forceinline__ prf_u32x3 raw64(prf_lds_cu32 *plane, u32 q) {
+    const u32 w = q >> 5;
+    const prf_u32x3 r = {plane[w], plane[w + 1], plane[w + 2]};
+    return r;
+}
+__device__ __forceinline__ u64 cut64(prf_u32x3 r, u32 q) {
+    const u32 sft = q & 31u;
+    return (u64)__builtin_amdgcn_alignbit(r.y, r.x, sft) | ((u64)__builtin_amdgcn_alignbit(r.z, r.y, sft) << 32);
+}
 struct WinCtx {
     prf_lds_cu32 *h, *l, *cof;
     const u32 *xw;  // mixed tile: the not-ACGT plane from window position 0 on (global memory); nullptr for clean tiles
@@ -312,78 +325,107 @@ __device__ __forceinline__ void win_verify_flag(const TileCtx &tc, const WinCtx 
     }
 }
 
-// group-task record, one flagged stream at window position q, every S-th aligned group of 8 examined: the examined
-// all-match groups that are the first of their run, if the run starts inside the tile.
-// The cheap part (which of the stream's groups qualify) is a loop of its own; the expensive part (run end, length,
-// primitive motif, row) then runs once per qualifying group -- almost always once per stream -- instead of once per group
-// index at which ANY lane of the wave has something.
-__device__ __forceinline__ void win_verify_group(const TileCtx &tc, const WinCtx &wc, u32 q, u32 k, u32 S) {
-    const u32 M = min_matches32(k, wc.min_repeats, wc.min_span);
+// ---- group-task records, in two stages (the upper half of the workgroup; verify_all drives them) ----
+// Stage A lists the wave's flagged streams, 4 bytes each: [10:0] stream (bit * 64 + lane), [19:11] k, [21:20] stride code.  The
+// list lies in R1 behind the window.  Stage B takes one stream per lane: ONE 64-position look says which of its examined
+// groups are all-match, the first examined one of their run, with the run's start inside the tile -- the LEADERS --, and
+// each leader is verified with the looks of its period tests issued in ONE batch before any of them is used.  A leader
+// goes into that batch as two registers (passed as its six fields it costs seven, and the kernel spills):
+//   [16:0] window position a of the run's start, [25:17] k, [30:26] nb = matches between a and the group, [31] k has a
+//   fourth cofactor;  [55:32] the cofactors k/p of k's first three primes (cof[k]: read beside the stream's look, so that
+//   nothing waits for the table), [57:56] j = the group's index in its stream, [62:58] e = matches seen directly behind
+//   the group by the stream's look (31: no mismatch seen there).
+constexpr u32 LEAD_CAP = 192u;  // flagged streams of one wave's list; a full list is worked off (stage B) and filled again
+constexpr u32 LEAD_OFF = (u32)SMEM_HDR + 2u * (u32)LW * 8u;  // byte offset of the two lists: R1 behind the window
+constexpr u32 LEAD_NO_END = 31u;
+
+// One flagged stream at window position q, every S-th aligned group of 8 examined.  Returns the leaders (bit j =
+// group j) whose looks stay inside the window, `far` = those whose looks may not (-> defer), nbs = 5 bits per group:
+// matches directly before it; m = mismatch bits of window positions q - 32 .. q + 31.
+__device__ __forceinline__ u32 win_leaders(const WinCtx &wc, u32 q, u32 k, u32 S, u64 m, u32 &nbs, u32 &far) {
     const u32 back = 8u * S;
-    const u64 m = win_mismatch64(wc, q - 32u, k);  // bit i = mismatch at window position q - 32 + i
-    const u32 cof_k = wc.cof[k];
-    u32 leaders = 0;  // bit j: group j of the stream is all-match, the first examined one of its run, and the run starts in the tile
-    u32 nbs = 0;      // 5 bits per group: matches directly before it
-    for (u32 j = 0; j < 4u; j += S) {
+    u32 leaders = 0;
+    nbs = 0;
+    far = 0;
+#pragma unroll
+    for (u32 j = 0; j < 4u; j++) {
         const u32 gb = 32u + 8u * j;  // bit of the group's first position
         const u64 lead = m << (64u - gb);  // bit 63 = the position directly before the group
         const u32 nb = lead ? (u32)__builtin_clzll(lead) : 64u;  // matches directly before it (>= 32 seen)
-        const bool ok = ((m >> gb) & 0xFFull) == 0 && nb < back && q - 32u + gb - nb >= WIN_LEAD;
-        leaders |= (ok ? 1u : 0u) << j;
+        const u32 a = q - 32u + gb - nb;
+        const bool ok = (j & (S - 1u)) == 0u && ((m >> gb) & 0xFFull) == 0 && nb < back && a >= WIN_LEAD;
+        const bool out = a + 2u * k + 96u > WIN_POS;
+        leaders |= (ok && !out ? 1u : 0u) << j;
+        far |= (ok && out ? 1u : 0u) << j;
         nbs |= (nb & 31u) << (5u * j);
     }
-    while (leaders) {
-        const u32 j = (u32)__builtin_ctz(leaders);
-        leaders &= leaders - 1;
-        const u32 gb = 32u + 8u * j, nb = (nbs >> (5u * j)) & 31u;
-        const u32 a = q - 32u + gb - nb;
-        // One batch of looks, issued together (one LDS round trip): the first 32 positions of the period test of up to three
-        // cofactors, and the 64 positions behind the first look for the run's end.  Primitive motif first: most group
-        // candidates are echoes of a short motif.
-        if (a + 2u * k + 96u > WIN_POS) {  // (the group itself is known to match)
-            defer(tc, wc.win0 + a, k, 0u, 0u, 1u, wc.win0 + (q - 32u + gb + 8u));
-            continue;
-        } else {
-            const u32 d1 = cof_k & 255u, d2 = (cof_k >> 8) & 255u, d3 = (cof_k >> 16) & 255u;
-            const u32 mm1 = win_mismatch32(wc, a, d1 ? d1 : 1u);
-            const u32 mm2 = win_mismatch32(wc, a, d2 ? d2 : 1u);
-            const u32 mm3 = win_mismatch32(wc, a, d3 ? d3 : 1u);
-            bool rep = false;
-            for (u32 ci = 0; ci < 4u && !rep; ci++) {
-                const u32 d = (cof_k >> (8u * ci)) & 255u;
-                if (d == 0) break;
-                const u32 need = k - d;
-                u32 mm = ci == 0 ? mm1 : (ci == 1 ? mm2 : (ci == 2 ? mm3 : win_mismatch32(wc, a, d)));
-                if (need < 32) mm &= (1u << need) - 1u;
-                rep = mm == 0;
-                for (u32 off = 32; off < need && rep; off += 32) {
-                    u32 m2 = win_mismatch32(wc, a + off, d);
-                    const u32 left = need - off;
-                    if (left < 32) m2 &= (1u << left) - 1u;
-                    rep = m2 == 0;
-                }
-            }
-            if (rep) continue;
-        }
-        const u64 seen = gb + 8u < 64u ? m >> (gb + 8u) : 0ull;  // bit i = mismatch at group end + i
-        u64 b;
-        if (seen) {
-            b = wc.win0 + (q - 32u + gb + 8u) + (u64)__builtin_ctzll(seen);
-        } else {
-            const u64 m2 = win_mismatch64(wc, q + 32u, k);  // (q + 32 + k + 96 <= WIN_POS for every stream of the tile)
-            if (m2) {
-                b = wc.win0 + (q + 32u) + (u64)__builtin_ctzll(m2);
-            } else {
-                u32 from = q + 96u;
-                if (!win_run_end(wc, from, k, b)) {
-                    defer(tc, wc.win0 + a, k, 0u, 0u, 0u, wc.win0 + from);
-                    continue;
-                }
-            }
-        }
-        if (b - (wc.win0 + a) < (u64)M) continue;
-        emit_row(tc, wc.win0 + a, b, k);
+    return leaders;
+}
+
+__device__ __forceinline__ u64 make_leader(u32 q, u32 k, u32 cof_k, u32 j, u32 nb, u64 m) {
+    const u32 gb = 32u + 8u * j;
+    const u64 seen = gb + 8u < 64u ? m >> (gb + 8u) : 0ull;  // bit i = mismatch at group end + i (24 - 8 j positions known)
+    const u32 e = seen ? (u32)__builtin_ctzll(seen) : LEAD_NO_END;
+    const u32 lo = (q - 32u + gb - nb) | (k << 17) | (nb << 26) | ((cof_k >> 24) ? 1u << 31 : 0u);
+    const u32 hi = (cof_k & 0xFFFFFFu) | (j << 24) | (e << 26);
+    return (u64)lo | ((u64)hi << 32);
+}
+
+// period d of the motif at window position a (positions a .. a+k-d-1 equal the ones d later), mm = the test's first 64
+// positions; a + 2 k + 96 <= WIN_POS.  Motif sizes up to 64 + d are decided by mm alone.
+__device__ __forceinline__ bool win_has_period(const WinCtx &wc, u32 a, u32 k, u32 d, u64 mm) {
+    const u32 need = k - d;
+    if (need < 64u) mm &= (1ull << need) - 1ull;
+    bool has = mm == 0;
+    for (u32 off = 64; off < need && has; off += 64) {
+        u64 m2 = win_mismatch64(wc, a + off, d);
+        const u32 left = need - off;
+        if (left < 64u) m2 &= (1ull << left) - 1ull;
+        has = m2 == 0;
     }
+    return has;
+}
+
+// One leader.  One batch of looks, issued together (one LDS round trip): the first 64 positions of the period test of the
+// first two cofactors -- the whole test for k <= 64 + d.  (A third cofactor's look and the look for the run's end are not in
+// the batch: with them the kernel needs more than its 80 registers, and few leaders get that far.)  Then: primitive motif
+// (most group candidates are echoes of a short motif and end here), run end, length filter, row.
+__device__ __forceinline__ void win_verify_leader(const TileCtx &tc, const WinCtx &wc, u64 item) {
+    const u32 lo = (u32)item, hi = (u32)(item >> 32);
+    const u32 a = lo & 0x1FFFFu, k = (lo >> 17) & 511u, nb = (lo >> 26) & 31u;
+    const u32 d1 = hi & 255u, d2 = (hi >> 8) & 255u, d3 = (hi >> 16) & 255u, j = (hi >> 24) & 3u, e = (hi >> 26) & 31u;
+    const u32 ge = a + nb + 8u;            // the group's end
+    const u32 q32 = ge + 24u - 8u * j;     // the end of the stream's look (q + 32 + k + 96 <= WIN_POS for every stream of the tile)
+    const u32 p1 = a + (d1 ? d1 : 1u), p2 = a + (d2 ? d2 : 1u);
+    prf_u32x3 ra = raw64(wc.h, a), sa = raw64(wc.l, a), r1 = raw64(wc.h, p1), s1 = raw64(wc.l, p1), r2 = raw64(wc.h, p2), s2 = raw64(wc.l, p2);
+    asm volatile("" : "+v"(ra), "+v"(sa), "+v"(r1), "+v"(s1), "+v"(r2), "+v"(s2));
+    const u64 ha = cut64(ra, a), la = cut64(sa, a);
+    u64 mm1 = (ha ^ cut64(r1, p1)) | (la ^ cut64(s1, p1)), mm2 = (ha ^ cut64(r2, p2)) | (la ^ cut64(s2, p2));
+    if (wc.xw) {
+        const u64 xa = xlook64(wc.xw, a);
+        mm1 |= xa | xlook64(wc.xw, p1);
+        mm2 |= xa | xlook64(wc.xw, p2);
+    }
+    bool rep = d1 && win_has_period(wc, a, k, d1, mm1);
+    if (!rep && d2) rep = win_has_period(wc, a, k, d2, mm2);
+    if (!rep && d3) rep = win_has_period(wc, a, k, d3, win_mismatch64(wc, a, d3));  // a third prime: k = 30, 42, 60, ...
+    if (!rep && (lo >> 31)) {  // a fourth: k >= 210
+        const u32 d4 = wc.cof[k] >> 24;
+        rep = win_has_period(wc, a, k, d4, win_mismatch64(wc, a, d4));
+    }
+    if (rep) return;
+    u64 b;
+    if (e != LEAD_NO_END) {
+        b = wc.win0 + ge + e;
+    } else {
+        u32 from = q32;
+        if (!win_run_end(wc, from, k, b)) {
+            defer(tc, wc.win0 + a, k, 0u, 0u, 0u, wc.win0 + from);
+            return;
+        }
+    }
+    if (b - (wc.win0 + a) < (u64)min_matches32(k, wc.min_repeats, wc.min_span)) return;
+    emit_row(tc, wc.win0 + a, b, k);
 }
 
 // Boundary pass.  A group task's run is found at the FIRST examined all-match group it contains.  For a run that starts
@@ -455,19 +497,85 @@ __device__ __forceinline__ void verify_all(prf_lds_cu64 *recs, u32 n_recs, prf_l
     // about as long as two passes over the flags plus one over the boundary items (lower half); a wave's pass costs the same
     // with 1 or 64 candidates.
     if (tid >= (u32)NTH / 2u) {
-        // ---- group-task records, alternating between the two waves
+        // ---- group-task records, alternating between the two waves.  A record's word has a bit per flagged stream, and a loop
+        // over a lane's own bits runs as often as the wave's unluckiest lane has bits.  So each wave first lists its flagged streams
+        // (stage A: a prefix sum of the lanes' bit counts, no look), then takes them one per lane from lane 0 up (stage B).  No
+        // barrier between the stages: a wave's LDS operations are carried out in the order it issues them, so stage B's reads of
+        // the wave's list follow stage A's writes to it, whichever lanes they come from (the fences only keep the compiler from
+        // moving them).  Every loop that holds a look is wave-uniform: lanes without work are masked.
         const u32 up = (u32)NTH - 1u - tid;  // 0 .. 127: thread 255, 254, ...
-        for (u32 idx = 2u * (up & 63u) + (up >> 6); idx < n_recs; idx += (u32)NTH / 2u) {
-            const u64 rec = recs[idx];
-            const u32 rl = (u32)rec & 63u, k = ((u32)rec >> 6) & 511u, sc = ((u32)rec >> 15) & 3u;
-            u32 word = (u32)(rec >> 17);
-            while (word) {
-                const u32 bit = (u32)__builtin_ctz(word);
-                word &= word - 1;
-                const u32 sq = (bit * 64u + rl) * T;
-                if (sq >= 32u || xw) win_verify_group(tc, wc, WIN_LEAD + sq, k, 1u << (sc - 1u));
-                else defer(tc, tc.tile_base, k, sc, 1u, 0u, 0ull);
+        const u32 hwl = tid & 63u;
+        prf_lds_u32 *list = (prf_lds_u32 *)(prf_smem + LEAD_OFF) + (up >> 6) * LEAD_CAP;
+        u32 idx = 2u * (up & 63u) + (up >> 6), word = 0, head = 0;
+        for (;;) {  // one round, unless the wave has more flagged streams than its list holds
+            u32 n_items = 0;  // wave-uniform
+            bool more;
+            // ---- stage A: (stream, k, stride code) of every flagged stream -> the wave's list; a lane's streams lie together
+            for (;;) {
+                if (word == 0u && idx < n_recs) {
+                    const u64 rec = recs[idx];
+                    idx += (u32)NTH / 2u;
+                    head = (u32)rec & 0x1FFFFu;  // lane, k, stride code
+                    word = (u32)(rec >> 17);
+                }
+                const u32 pc = (u32)__builtin_popcount(word);
+                u32 at = n_items, total = 0;
+#pragma unroll
+                for (u32 b = 0; b < 6u; b++) {  // (pc <= 32)
+                    const u64 bal = __builtin_amdgcn_ballot_w64(((pc >> b) & 1u) != 0);
+                    at += __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0)) << b;
+                    total += (u32)__builtin_popcountll(bal) << b;
+                }
+                u32 room = at < LEAD_CAP ? LEAD_CAP - at : 0u;  // (a lane keeps the streams that do not fit for the next round)
+                for (; word && room; room--) {
+                    const u32 bit = (u32)__builtin_ctz(word);
+                    word &= word - 1;
+                    list[at++] = (bit * 64u + (head & 63u)) | ((head >> 6) << 11);
+                }
+                n_items = n_items + total < LEAD_CAP ? n_items + total : LEAD_CAP;
+                more = __builtin_amdgcn_ballot_w64(word != 0u || idx < n_recs) != 0ull;
+                if (!more || n_items == LEAD_CAP) break;
             }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            PRF_VSTAMP(14);
+            // ---- stage B: one listed stream per lane: one look says which of its groups are leaders; then leader by leader
+            // (almost always one per stream)
+            for (u32 i0 = 0; i0 < n_items; i0 += 64u) {
+                u32 leaders = 0, nbs = 0, far = 0, cof_k = 0, q = 0, k = 0;
+                u64 m = 0;
+                if (i0 + hwl < n_items) {
+                    const u32 it = list[i0 + hwl], sq = (it & 2047u) * T, sc = (it >> 20) & 3u;
+                    k = (it >> 11) & 511u;
+                    q = WIN_LEAD + sq;
+                    if (sq >= 32u || xw) {
+                        // bit i = mismatch at window position q - 32 + i; one round trip with the cofactors
+                        prf_u32x3 r0 = raw64(wc.h, q - 32u), r1 = raw64(wc.l, q - 32u), r2 = raw64(wc.h, q - 32u + k), r3 = raw64(wc.l, q - 32u + k);
+                        cof_k = wc.cof[k];
+                        asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(cof_k));
+                        m = (cut64(r0, q - 32u) ^ cut64(r2, q - 32u + k)) | (cut64(r1, q - 32u) ^ cut64(r3, q - 32u + k));
+                        if (xw) m |= xlook64(xw, q - 32u) | xlook64(xw, q - 32u + k);
+                        leaders = win_leaders(wc, q, k, 1u << (sc - 1u), m, nbs, far);
+                        while (far) {  // (the group itself is known to match)
+                            const u32 j = (u32)__builtin_ctz(far);
+                            far &= far - 1;
+                            defer(tc, wc.win0 + (q + 8u * j - ((nbs >> (5u * j)) & 31u)), k, 0u, 0u, 1u, wc.win0 + (q + 8u * j + 8u));
+                        }
+                    } else {
+                        defer(tc, tc.tile_base, k, sc, 1u, 0u, 0ull);  // (a clean tile's first stream: see the flags below)
+                    }
+                }
+                while (__builtin_amdgcn_ballot_w64(leaders != 0u) != 0ull) {
+                    if (leaders) {
+                        const u32 j = (u32)__builtin_ctz(leaders);
+                        leaders &= leaders - 1;
+                        win_verify_leader(tc, wc, make_leader(q, k, cof_k, j, (nbs >> (5u * j)) & 31u, m));
+                    }
+                }
+            }
+            if (!more) break;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
         }
     } else {
         // ---- exact tasks' flags: (lane, stream bit, task), dealt to the threads one by one: a wave runs the body once per 64

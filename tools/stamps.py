@@ -51,7 +51,9 @@ print('records per tile: mean %.1f p10 %d p50 %d p90 %d p99 %d max %d; share <=6
 import collections
 print('joint (ceil(flags/64), ceil(recs/64)) shares:', sorted(((k, round(v / len(nf), 3)) for k, v in collections.Counter(zip(((nf + 63) // 64).tolist(), ((nr + 63) // 64).tolist())).items()), key=lambda kv: -kv[1])[:12])
 for w in range(4):
-    print('wave', w, 'verify: flags part %d, records / boundary part %d' % (int(np.median(d[:, w, 14] - d[:, w, 4])), int(np.median(d[:, w, 5] - d[:, w, 14]))))
+    # (stamp 14: the flag waves 0, 1 set it behind the flags, the record waves 2, 3 between their stages A and B)
+    print('wave', w, ('verify: flags part %d, boundary part %d' if w < 2 else 'verify: records stage A %d, stage B %d') % (
+        int(np.median(d[:, w, 14] - d[:, w, 4])), int(np.median(d[:, w, 5] - d[:, w, 14]))))
 for w in range(4):
     print('wave', w, 'cycles inside the exact-task functions (sum over the wave\'s exact tasks): median', int(np.median(d[:, w, 15])))
 
