@@ -19,6 +19,17 @@ __device__ __forceinline__ u64 make_rec(u32 lane, u32 k, u32 sc, u32 word) {
     return (u64)(lane | (k << 6) | (sc << 15)) | ((u64)word << 17);
 }
 
+// The same record as the two dwords that are stored, for a tag = make_rec_tag(lane, k, sc) -- or that of the task's first motif size
+// plus (i << 6) for size k0 + i, which cannot carry out of the k field while k0 + i <= PRF_VMAX_K.
+typedef u32 prf_u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) prf_u32x2 prf_lds_u32x2;
+static_assert(PRF_VMAX_K < (1 << 9), "k is a 9-bit field of a record");
+__device__ __forceinline__ u32 make_rec_tag(u32 lane, u32 k, u32 sc) { return lane | (k << 6) | (sc << 15); }
+__device__ __forceinline__ prf_u32x2 make_rec_halves(u32 tag, u32 word) {
+    prf_u32x2 r = {tag | (word << 17), word >> 15};
+    return r;
+}
+
 // dynamic LDS: [header][R1: image / window][recs][row keys][row motif sizes][all-N stream masks][flag lists, counts][boundary items][cofactors]
 extern __shared__ __attribute__((aligned(16))) unsigned char prf_smem[];
 using prf_layout::SMEM_HDR;

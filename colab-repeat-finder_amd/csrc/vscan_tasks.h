@@ -7,16 +7,59 @@ struct Emit {
     prf_lds_u64 *recs;       // the tile's record list in LDS, REC_CAP records
     prf_lds_u32 *cnt;        // this tile's counter set
     int lane;
+#ifdef PRF_STAMPS
+    u64 t_push_g = 0, t_push_f = 0;  // cycles this wave spent handing over the answers of its group / exact and coarse tasks (this tile)
+#endif
 
     // Exact tasks: the lanes' words of ONE task -> flags (lane | stream bit << 6 | task << 11) appended to the tile's list.
-    // ONE reservation per task (the stamps of the first version showed 2.7 k cycles per task in here against 2 k in the task
-    // itself: an LDS atomic round trip per round of the loop): a first pass of ballots counts the flags level by level (level j =
-    // the lanes with more than j flags), one atomic reserves them, a second pass places them -- level j behind the levels below
-    // it, a lane's flag behind those of the lower lanes.  Flags beyond the list's capacity (a tile of long runs) are verified on
-    // the spot with the general routine.
+    // Each lane reserves for itself, as emit_row does: the lanes with flags issue ONE returning LDS add on the list's counter in one
+    // instruction (the hardware hands every lane its own base), then write their flags behind that base; the loop runs as often
+    // as the wave's unluckiest lane has flags.  (The first version reserved per round of the loop: 2.7 k cycles per task in here
+    // against 2 k in the task itself.)  That puts a lane's flags side by side in the list, where the old placement had them level
+    // by level in tile order.  A task in which some lane has more than DENSE_FLAGS flags (a tile of clusters; 2 % of the tasks
+    // otherwise) keeps the old placement (push_flags_levels): measured on chr22-real, whose kernel time is its densest tile, that
+    // took the kernel from +7 % to +2 % against the parent.  Why the order matters there was not established (the verification
+    // takes one flag per thread, and a lane's streams lie 256 bytes apart in the window, the same LDS bank: a guess); the
+    // threshold was not swept.  Flags beyond the list's capacity (a tile of long runs) are verified on the spot with the general
+    // routine.
+    static constexpr u32 DENSE_FLAGS = 4;
     __device__ __forceinline__ void push_flags(u32 word, u32 e, u32 k, prf_lds_u32 *flag_words) {
         typedef __attribute__((address_space(3))) unsigned short prf_lds_u16;
         prf_lds_u16 *list = (prf_lds_u16 *)flag_words;
+        const u32 pc = (u32)__builtin_popcount(word);
+        if (__builtin_amdgcn_ballot_w64(pc > DENSE_FLAGS) != 0) {  // wave-uniform
+            push_flags_levels(word, e, k, list);
+            return;
+        }
+        if (word == 0) return;
+        u32 at = atomicAdd((u32 *)(cnt + CNT_FLAGS), pc);
+        const u32 tag = (u32)lane | (e << 11);
+        if (at + pc <= (u32)FLAG_CAP) {
+            prf_lds_u16 *p = list + at;
+            do {
+                *p++ = (unsigned short)(tag | ((u32)__builtin_ctz(word) << 6));
+                word &= word - 1;
+            } while (word);
+            return;
+        }
+        do {  // the list is full: what still fits is listed
+            const u32 bit = (u32)__builtin_ctz(word);
+            word &= word - 1;
+            if (at < (u32)FLAG_CAP) {
+                list[at] = (unsigned short)(tag | (bit << 6));
+            } else {
+                atomicAdd((u32 *)(cnt + CNT_EARLY), 1u);
+                verify_stream(reinterpret_cast<const TileCtx *>(prf_smem)->tile_base + (u64)(bit * 64u + (u32)lane) * T, k, 0u);
+            }
+            at++;
+        } while (word);
+    }
+
+    // The placement for dense tasks: ONE reservation for the wave.  A first pass of ballots counts the flags level by level (level
+    // j = the lanes with more than j flags), one atomic reserves them, a second pass places them -- level j behind the levels below
+    // it, a lane's flag behind those of the lower lanes: neighbours in the list are neighbours in the tile.  About 70
+    // wave-instructions for a task of two levels.
+    __device__ __forceinline__ void push_flags_levels(u32 word, u32 e, u32 k, __attribute__((address_space(3))) unsigned short *list) {
         const u32 pc = (u32)__builtin_popcount(word);
         u32 total = 0;  // wave-uniform
         for (u32 j = 0;; j++) {
@@ -24,7 +67,6 @@ struct Emit {
             if (bal == 0) break;
             total += (u32)__builtin_popcountll(bal);
         }
-        if (total == 0) return;
         u32 base = 0;
         if (lane == 0) base = atomicAdd((u32 *)(cnt + CNT_FLAGS), total);
         base = (u32)__builtin_amdgcn_readfirstlane((int)base);
@@ -46,28 +88,56 @@ struct Emit {
         }
     }
 
-    // Group tasks: one 32-bit word per lane (bit b = stream b*64 + lane is flagged for motif size k) -> one record per lane
-    // with a non-zero word, appended to the tile's list (one LDS atomic per call); a full list -> verified on the spot.
-    __device__ __forceinline__ void push_word(u32 word, u32 k, u32 sc) {
-        const u64 bal = __builtin_amdgcn_ballot_w64(word != 0);
-        if (bal == 0) return;
-        const u32 n = (u32)__builtin_popcountll(bal);
-        u32 base = 0;
-        if (lane == (int)__builtin_ctzll(bal)) base = atomicAdd((u32 *)(cnt + CNT_RECS), n);
-        base = (u32)__builtin_amdgcn_readlane((int)base, (int)__builtin_ctzll(bal));
-        if (word) {
-            const u32 idx = base + __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0));
-            if (idx < (u32)REC_CAP) {
-                recs[idx] = make_rec((u32)lane, k, sc, word);
+    // Group tasks: one 32-bit word per lane and motif size k0 + i (bit b = stream b*64 + lane is flagged for that size; zero for a
+    // size the task does not have) -> one record per non-zero word, appended to the tile's list.  ONE reservation per task and
+    // lane: a lane with n records adds n to the list's counter -- the lanes that have any do so in one instruction, without
+    // ballot, readlane or mbcnt -- and writes them behind its base in size order.  (One reservation per SIZE through the first
+    // lane with a record: 25 wave-instructions and an LDS round trip of its own for each of a task's 8 sizes.  One per task with
+    // the eight ballots kept across the atomic: 37 more SGPRs than the kernel has, slower.)  A lane whose slots reach past the
+    // list's capacity lists what fits and remembers the rest; those words are verified on the spot behind a wave-uniform test,
+    // size by size with the general routine called from the kernel itself, as before.  (With the calls inside the lanes' own
+    // branch the words lived in scratch memory around them; through a routine of their own every call saved and restored that
+    // routine's registers in scratch memory, 3 k cycles in the scan phase of chr22-real's densest tile.)
+    template <int N>  // 8, or 4 for a task of one half
+    __device__ __forceinline__ void push_words(const u32 (&w)[N], u32 k0, u32 sc) {
+        u32 n = 0;
+        static_for<0, N>([&](auto ic) { n += w[decltype(ic)::value] != 0 ? 1u : 0u; });
+        const u32 tag = make_rec_tag((u32)lane, k0, sc);
+        u32 late = 0;  // bit i: word i found no room in the list
+        if (n) {
+            u32 idx = atomicAdd((u32 *)(cnt + CNT_RECS), n);
+            if (idx + n <= (u32)REC_CAP) {
+                prf_lds_u32x2 *at = (prf_lds_u32x2 *)(recs + idx);
+                static_for<0, N>([&](auto ic) {
+                    constexpr u32 i = (u32)decltype(ic)::value;
+                    if (w[i]) *at++ = make_rec_halves(tag + (i << 6), w[i]);
+                });
             } else {
-                atomicAdd((u32 *)(cnt + CNT_EARLY), 1u);
-                const u64 tile_base = reinterpret_cast<const TileCtx *>(prf_smem)->tile_base;
-                while (word) {
-                    const u32 bit = (u32)__builtin_ctz(word);
-                    word &= word - 1;
-                    verify_stream(tile_base + (u64)(bit * 64u + (u32)lane) * T, k, sc);
-                }
+                static_for<0, N>([&](auto ic) {
+                    constexpr u32 i = (u32)decltype(ic)::value;
+                    if (w[i]) {
+                        if (idx < (u32)REC_CAP) ((prf_lds_u32x2 *)recs)[idx] = make_rec_halves(tag + (i << 6), w[i]);
+                        else late |= 1u << i;
+                        idx++;
+                    }
+                });
             }
+        }
+        // the list is full (wave-uniform test, cold): the words without a slot go size by size through the general routine
+        if (__builtin_amdgcn_ballot_w64(late != 0) != 0) {
+            const u64 tile_base = reinterpret_cast<const TileCtx *>(prf_smem)->tile_base;
+            static_for<0, N>([&](auto ic) {
+                constexpr u32 i = (u32)decltype(ic)::value;
+                if ((late >> i) & 1u) {
+                    atomicAdd((u32 *)(cnt + CNT_EARLY), 1u);
+                    u32 word = w[i];
+                    do {
+                        const u32 bit = (u32)__builtin_ctz(word);
+                        word &= word - 1;
+                        verify_stream(tile_base + (u64)(bit * 64u + (u32)lane) * T, k0 + i, sc);
+                    } while (word);
+                }
+            });
         }
     }
 };
@@ -108,8 +178,9 @@ __device__ __forceinline__ prf_lds_cu4 *slot_after(prf_lds_cu4 *first, int a) {
 // ---- group task: motif sizes k0 .. k0+7 (those in `valid`), the 8-row blocks 0 .. 3 of the stream ----
 // S1: every block is examined (stride 1) and a group counts only if the group before it was not all-match; otherwise
 // (stride 2 / 4, and every task of a mixed tile) every examined all-match group counts.  The per-size words are OR-ed over the
-// blocks and leave as records at the end of the task.  The eight sizes are computed as two halves of four, the rows of the
-// second half's last slot loaded in between: 40 row registers instead of 48, four OR chains interleaved.
+// blocks and leave as records at the end of the task, through one reservation per lane (Emit::push_words).  The eight sizes are
+// computed as two halves of four, the rows of the second half's last slot loaded in between: 40 row registers instead of 48,
+// four OR chains interleaved.
 // HALF: only the sizes k0 .. k0+3 (a task whose second half wants another stride, or lies beyond the largest motif size).
 template <int NC, bool S1, bool HALF>
 __device__ __forceinline__ void group_task(prf_lds_cu4 *vimg, int lane, u32 k0, u32 valid, u32 stride, u32 allow, Emit &em) {
@@ -174,10 +245,24 @@ __device__ __forceinline__ void group_task(prf_lds_cu4 *vimg, int lane, u32 k0, 
         }
     }
     const u32 sc = stride == 1 ? 1u : (stride == 2 ? 2u : 3u);
+#ifdef PRF_STAMPS
+    asm volatile("" ::"v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]));  // (the body ends here)
+    if constexpr (!HALF) asm volatile("" ::"v"(acc[4]), "v"(acc[5]), "v"(acc[6]), "v"(acc[7]));
+    const u64 tp0 = __builtin_amdgcn_s_memtime();
+#endif
     static_for<0, (HALF ? 4 : 8)>([&](auto kc) {
         constexpr int kk = decltype(kc)::value;
-        if ((valid >> kk) & 1u) em.push_word(acc[kk] & allow, k0 + (u32)kk, sc);  // wave-uniform condition
+        acc[kk] = ((valid >> kk) & 1u) ? acc[kk] & allow : 0u;  // (wave-uniform choice)
     });
+    if constexpr (HALF) {
+        const u32 w4[4] = {acc[0], acc[1], acc[2], acc[3]};
+        em.push_words(w4, k0, sc);
+    } else {
+        em.push_words(acc, k0, sc);
+    }
+#ifdef PRF_STAMPS
+    em.t_push_g += __builtin_amdgcn_s_memtime() - tp0;
+#endif
 }
 
 // OR of the mismatch words of the M rows t .. t+M-1.  mm is indexed by row + 1 (mm[0] = the row before the stream),
@@ -433,14 +518,17 @@ __device__ __forceinline__ void run_tasks(prf_lds_cu4 *vimg, prf_lds_u32 *hotw, 
             const u64 tc0 = __builtin_amdgcn_s_memtime();
             const u32 word = exact_any<NC>(vimg, lane, relax, task.k0, task.kind);
             asm volatile("" ::"v"(word));
-            t_call += __builtin_amdgcn_s_memtime() - tc0;
+            const u64 tc1 = __builtin_amdgcn_s_memtime();
+            t_call += tc1 - tc0;
             em.push_flags(word & allow, task.item0, task.k0, hotw);
+            em.t_push_f += __builtin_amdgcn_s_memtime() - tc1;
 #else
             em.push_flags(exact_any<NC>(vimg, lane, relax, task.k0, task.kind) & allow, task.item0, task.k0, hotw);
 #endif
         }
     }
 #ifdef PRF_STAMPS
-    if (dbg && lane == 0) dbg[15] = t_call;
+    // slot 15: [21:0] cycles inside the exact-task functions, [42:22] in push_flags, [63:43] in the group tasks' pushes
+    if (dbg && lane == 0) dbg[15] = (t_call & 0x3FFFFFull) | ((em.t_push_f & 0x1FFFFFull) << 22) | ((em.t_push_g & 0x1FFFFFull) << 43);
 #endif
 }

@@ -55,7 +55,11 @@ for w in range(4):
     print('wave', w, ('verify: flags part %d, boundary part %d' if w < 2 else 'verify: records stage A %d, stage B %d') % (
         int(np.median(d[:, w, 14] - d[:, w, 4])), int(np.median(d[:, w, 5] - d[:, w, 14]))))
 for w in range(4):
-    print('wave', w, 'cycles inside the exact-task functions (sum over the wave\'s exact tasks): median', int(np.median(d[:, w, 15])))
+    # slot 15: [21:0] inside the exact-task functions, [42:22] in push_flags, [63:43] in the group tasks' pushes (sums over the wave's tasks)
+    body, pf, pg = d[:, w, 15] & 0x3FFFFF, (d[:, w, 15] >> 22) & 0x1FFFFF, (d[:, w, 15] >> 43) & 0x1FFFFF
+    print('wave', w, 'cycles inside the exact-task functions (sum over the wave\'s exact tasks): median', int(np.median(body)))
+    print('wave', w, 'cycles in pushes: exact/coarse tasks median %d mean %.0f, group tasks median %d mean %.0f; both, share of the wave\'s tile time %.3f' % (
+        int(np.median(pf)), pf.mean(), int(np.median(pg)), pg.mean(), np.median((pf + pg) / np.maximum(1, d[:, w, 7] - d[:, w, 0]))))
 
 # slot utilisation from the chip-wide 100 MHz counter (slots 12 / 13 = workgroup start / end)
 rs = d[:, :, 12].min(axis=1); re = d[:, :, 13].max(axis=1)
