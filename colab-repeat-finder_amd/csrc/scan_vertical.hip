@@ -29,7 +29,8 @@
 //     question per (stream, motif size): "may a reportable run be found from this stream?" --
 //      * exact task, one motif size k with M(k) = M <= 8 (compiled per (k, M)): mismatch word per row
 //        (2 operations), sliding OR over exactly M rows; a row whose M successors all match and whose predecessor
-//        does not is the start of a run of >= M.
+//        does not is the start of a run of >= M.  k = 2, 3, 4 on a clean tile leave out the starts whose run is the
+//        echo of a shorter motif (tested once per segment of start rows, vscan_tasks.h): never a row.
 //      * coarse task, one motif size with 9 <= M <= 14: the same on aligned groups of 2 or 4 rows (a run of >= M rows
 //        holds floor((M + 1) / G) - 1 consecutive all-match groups).
 //      * group task, 8 motif sizes k0..k0+7 with M(k) >= 15: a run of >= 15 matches contains an aligned

@@ -289,10 +289,23 @@ __device__ __forceinline__ u32 window_or(const u32 (&mm)[LM], const u32 (&o3)[LO
 // (round 2 read all 60 rows first: 128 VGPRs, four workgroups per CU).
 // relax (mixed tile): a stream whose first M rows all match counts as well -- together with the starts that is "some M
 // matching rows begin in this stream", which no added match (a not-ACGT position reads as A) can take away.
+// K = 2, 3, 4 (ECHO) on a clean tile: a start whose run is the echo of a shorter motif -- its K letters have the period D = K / p,
+// p the one prime in K; the verification would find that and drop the candidate -- is not flagged.  A run that starts at row t
+// covers the rows t .. t+M-1+K, all of period K, so any K consecutive letters inside it are conjugates of one word and have the
+// period D or none of them has: the test may be made at any row j in t .. t+M.  It is made once per segment of SEG start rows,
+// (j - SEG, j] for j = 0, SEG, .. T, at row j (prim: the K - D mismatch words at distance D from row j on, OR-ed): SEG <= M + 1, so
+// j <= t + M, and two starts lie at least M + 1 rows apart, so a segment holds at most one.  The starts are collected per
+// segment with the one operation per row they cost anyway, and hot |= seg & prim closes the segment: 3 - 5 operations per
+// segment instead of 3 - 4 per row.  A mixed tile suppresses nothing (a not-ACGT position reads as A: the true start may lie
+// where the image sees the middle of a run).  Lane 0's conservative row -1 stays: an echo is never a row, wherever it began.
 // Not inlined: one compact function per (K, M), called by the one wave that runs the task.
 template <int K, int M, int NC>
 __device__ __attribute__((noinline)) u32 exact_stream(prf_lds_cu4 *vimg, int lane, bool relax) {
     constexpr int PS = RG * NC;
+    constexpr bool ECHO = K >= 2 && K <= 4;
+    constexpr int D = K == 4 ? 2 : 1;                               // K / p
+    constexpr int SEG = M + 1 >= 8 ? 8 : (M + 1 >= 4 ? 4 : 2);      // largest power of two <= min(M + 1, 8)
+    static_assert(!ECHO || (SEG <= M + 1 && T % SEG == 0 && K - 1 + T < T + M - 1 + K), "the sample lies inside the run and the rows read");
     constexpr int NM = T + M - 1;            // mismatch words of rows 0 .. NM-1
     constexpr int NG = (NM + K + 3) / 4;     // 16-byte slots of rows read
     static_assert(4 * NG <= 2 * T, "an exact task reads its own lane and the next one");
@@ -303,6 +316,9 @@ __device__ __attribute__((noinline)) u32 exact_stream(prf_lds_cu4 *vimg, int lan
     u32 mm[NM + 1];
     u32 o3[NM + 1];
     u32 hot = 0, prev = 0;  // prev: the window one row earlier
+    u32 seg = 0;            // (ECHO) the starts of the current segment
+    u32 prim[ECHO ? T / SEG + 1 : 1];  // (ECHO) prim[j / SEG]: the K letters at row j are no power of a shorter word
+    const u32 no_echo = relax ? ~0u : 0u;  // a mixed tile suppresses nothing (wave-uniform)
     auto load_slot = [&](auto gc) {
         constexpr int g = decltype(gc)::value;
         if constexpr (g < NG) {
@@ -319,6 +335,16 @@ __device__ __attribute__((noinline)) u32 exact_stream(prf_lds_cu4 *vimg, int lan
         __builtin_amdgcn_sched_barrier(0);
         static_for<0, 4>([&](auto jc) {
             constexpr int i = 4 * g + decltype(jc)::value - K;  // the mismatch row whose partner row has just arrived
+            if constexpr (ECHO && i >= 0 && i <= T && i % SEG == 0) {
+                // the sample of the segment that ends at row i: the rows i .. i+K-1 (all here) against the ones D further on
+                u32 n = no_echo;
+                static_for<0, K - D>([&](auto qc) {
+                    constexpr int q = i + decltype(qc)::value;
+                    n = or_xor(n, r0[q], r0[q + D]);
+                    n = or_xor(n, r1[q], r1[q + D]);
+                });
+                prim[i / SEG] = n;
+            }
             if constexpr (i == -1) {
                 // Row -1 of stream (lane, b) is row T-1 of stream (lane-1, b); for lane 0 it is row T-1 of stream (63, b-1):
                 // lane 63's word one bit up, with bit 0 (the previous tile's last stream) unknown -> "mismatch", verification
@@ -339,9 +365,22 @@ __device__ __attribute__((noinline)) u32 exact_stream(prf_lds_cu4 *vimg, int lan
                 constexpr int t = i - (M - 1);  // the window whose last row this is
                 if constexpr (t >= -1 && t < T) {
                     const u32 win = window_or<M, t>(mm, o3);
-                    if constexpr (t >= 0) hot = bitop3<(TA | (~TB & TC)) & 0xFF>(hot, win, prev);  // hot | (~win & prev)
-                    if constexpr (t == 0) {
-                        if (relax) hot |= ~win;
+                    if constexpr (!ECHO) {
+                        if constexpr (t >= 0) hot = bitop3<(TA | (~TB & TC)) & 0xFF>(hot, win, prev);  // hot | (~win & prev)
+                        if constexpr (t == 0) {
+                            if (relax) hot |= ~win;
+                        }
+                    } else if constexpr (t >= 0) {
+                        // the same operation per row, into the segment (t - SEG, t] that ends at the next multiple of SEG
+                        if constexpr (t == 0 || t % SEG == 1) seg = ~win & prev;
+                        else seg = bitop3<(TA | (~TB & TC)) & 0xFF>(seg, win, prev);  // seg | (~win & prev)
+                        if constexpr (t == 0) {
+                            if (relax) seg |= ~win;
+                        }
+                        // the segment's last start row (the one that ends at row T stops at T - 1): at most one start in it, and
+                        // the sampled row lies inside that start's run
+                        if constexpr (t % SEG == 0 || t == T - 1)
+                            hot = bitop3<(TA | (TB & TC)) & 0xFF>(hot, seg, prim[(t + SEG - 1) / SEG]);  // hot | (seg & prim)
                     }
                     prev = win;
                 }
