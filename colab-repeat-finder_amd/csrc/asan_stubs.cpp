@@ -1,4 +1,4 @@
-// asan_stubs.cpp -- what the host-only sanitizer build (make asan) needs from api.cpp: the error string.
+// asan_stubs.cpp -- what the host-only sanitizer build (make asan) needs from context.cpp: the error string.
 #include <cstdarg>
 #include <cstdio>
 #include <string>

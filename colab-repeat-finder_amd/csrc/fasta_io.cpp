@@ -23,7 +23,7 @@
 
 #include "../../include/prf.h"
 
-int prf_set_error(int code, const char *fmt, ...);  // api.cpp
+int prf_set_error(int code, const char *fmt, ...);  // context.cpp
 
 // sequence bytes: malloc'ed, never zero-filled, always 8 bytes of slack behind size() for word-wide stores
 struct prf_seq {

@@ -1,5 +1,5 @@
-// prf_ctx.h -- what the host translation units of libprf that talk to the device (api.cpp, interrupted.cpp, periodicity_host.cpp,
-// dotplot_host.cpp) share and nobody else sees: the context, error reporting, the C-boundary guard, parameter checks, a scoped
+// prf_ctx.h -- what the host translation units of libprf that talk to the device (context.cpp, genome.cpp, scan_host.cpp,
+// literal_host.cpp, handoff.cpp, interrupted.cpp, periodicity_host.cpp, dotplot_host.cpp) share and nobody else sees: the context, error reporting, the C-boundary guard, parameter checks, a scoped
 // device array, the refusal while pipelined scans are in flight, the stats of a lane that waits for its own kernels.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,7 +10,7 @@
 #include "../../include/prf.h"
 #include "prf_host.h"
 
-// Sets the calling thread's error text (prf_last_error) and returns `code`.  Defined in api.cpp; fasta_io.cpp reports through it too.
+// Sets the calling thread's error text (prf_last_error) and returns `code`.  Defined in context.cpp; fasta_io.cpp reports through it too.
 int prf_set_error(int code, const char *fmt, ...);
 static constexpr auto &fail = prf_set_error;
 
@@ -48,7 +48,7 @@ static int check_params(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, u32 k
     return PRF_OK;
 }
 
-// One contig of a resident genome as the host paths outside api.cpp see it (the genome's own struct stays private to api.cpp)
+// One contig of a resident genome as the matrix products see it (the genome's own struct, genome.h, stays private to the scan's host files)
 struct prf_contig_view {
     prf_ctx *ctx;
     prf_planes planes;  // linear planes; at least kmax_hint / 64 + 8 readable words behind them
@@ -73,6 +73,10 @@ struct dev_array {
         return PRF_OK;
     }
 };
+
+// A pinned host counter block (h_counters, h_async): PRF_CNT_N counters, then the scan's serial number in the word at PRF_CNT_N
+static const u64 PRF_CNT_BLOCK_WORDS = PRF_CNT_N + 8;  // words of a block
+static const u64 PRF_CNT_SPARE = PRF_CNT_N + 2;        // first of its spare words: staging for small copies to and from the device
 
 struct prf_ctx {
     int dev = -1;

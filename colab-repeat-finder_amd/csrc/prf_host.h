@@ -1,4 +1,4 @@
-// prf_host.h -- launch wrappers shared between the kernel translation units and the host ones that call them (api.cpp,
+// prf_host.h -- launch wrappers shared between the kernel translation units and the host ones that call them (context.cpp, genome.cpp, scan_host.cpp, literal_host.cpp, handoff.cpp,
 // interrupted.cpp, periodicity_host.cpp, dotplot_host.cpp, dotpair_host.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
