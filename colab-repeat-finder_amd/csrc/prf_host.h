@@ -1,5 +1,5 @@
 // prf_host.h -- launch wrappers shared between the kernel translation units and the host ones that call them (context.cpp, genome.cpp, scan_host.cpp, literal_host.cpp, handoff.cpp,
-// interrupted.cpp, periodicity_host.cpp, dotplot_host.cpp, dotpair_host.cpp).
+// interrupted.cpp, periodicity_host.cpp, dotplot_host.cpp, dotpair_host.cpp, dotruns_host.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -184,3 +184,31 @@ struct prf_dotpair_args {
     u32 tile_rows, span_words, halo, n_spans;  // set by the launch wrapper (prf_dotplot_shape_for)
 };
 hipError_t prf_launch_dotpair(hipStream_t s, prf_dotpair_args a, bool want_bits);
+
+// diagonal runs of the dot plot of two ranges as a list (dotruns.hip): the maximal runs of raw cells along (+1, +1)
+// (dir 1) and (+1, -1) (dir 2) of the na x nb rectangle whose start cell lies in window rows x columns; the ranges, the strand and
+// the fields that prf_dotpair_args has too mean the same.
+struct prf_dotrun_dev {       // = prf_dotrun
+    u64 row, col, len;
+    u32 dir, reserved;
+};
+enum { PRF_DR_RUNS = 0, PRF_DR_LONG = 1, PRF_DR_N = 2 };   // the call's two counters: runs found, entries of the long list
+struct prf_dotruns_args {
+    prf_planes pl;
+    u64 a_g_begin, na, b_g_begin, nb;
+    u64 col0, col1;
+    u64 lrow0, lrow1;         // rows of this launch (the last launch ends with the window); lrow0 - row0 is a multiple of 64
+    u64 words_per_row;
+    u64 min_len;
+    u32 strand, directions;
+    u32 p;                    // probe depth: min(min_len, PRF_DOTRUN_PROBE)
+    u32 span_words, n_spans;  // set by the launch wrapper
+    prf_dotrun_dev *dst;      // `capacity` rows; runs behind them are counted, not written
+    u64 capacity;
+    prf_dotrun_dev *longs;    // runs still going after PRF_DOTRUN_FOLLOW cells: start, cells so far, direction
+    u64 long_cap;
+    u64 *counters;            // PRF_DR_N words, zeroed by the caller
+};
+hipError_t prf_launch_dotruns_find(hipStream_t s, prf_dotruns_args a);
+// one wave per entry of the long list; n_long = min(the list's count, long_cap), read by the caller
+hipError_t prf_launch_dotruns_long(hipStream_t s, const prf_dotruns_args &a, u64 n_long);

@@ -11,6 +11,9 @@ Also beyond it: --versus X plots the inputs (rows) against another sequence or i
 --strand - compares with the complement of the columns' bases, so that an inverted repeat shows as an anti-diagonal; --strand both
 draws the cells that only the minus strand keeps in a second colour:
     plot_dot_plot.py -R genome.fa chr22:1000-3000 --versus chr21:5000-6500 --strand both -o pair.png
+And --runs-tsv lists what the picture shows as coordinates: every maximal diagonal or anti-diagonal run of matching cells of at
+least --min-run cells, one line each.  With --runs-tsv and no -o no image is drawn, and no limit on the length applies:
+    plot_dot_plot.py -R genome.fa chr22:20000000-21000000 --versus chr22:30000000-31000000 --strand both --runs-tsv runs.tsv --min-run 40
 """
 import argparse
 import gzip
@@ -184,12 +187,39 @@ def density_lines(name, begin, n, block, counts, col_begin=None, n_cols=None):
                f"{col_begin + min(n_cols, (c + 1) * block)}\t{int(counts[r, c])}\n")
 
 
+def run_lines(name, begin, x_name, x_begin, strand, runs):
+    """The --runs-tsv lines of a list of runs (fields row, col, len, dir): name, a_start, a_end, X's name, b_start, b_end, strand,
+    direction, length -- genomic coordinates, ends exclusive, the columns' in forward coordinates on both strands: an anti run
+    (row + s, col - s) covers columns col - len + 1 .. col."""
+    for row, col, length, direction in zip(*(runs[f].tolist() for f in ("row", "col", "len", "dir"))):
+        b_start = x_begin + (col if direction == 1 else col - length + 1)
+        yield (f"{name}\t{begin + row}\t{begin + row + length}\t{x_name}\t{b_start}\t{b_start + length}\t{strand}\t"
+               f"{'main' if direction == 1 else 'anti'}\t{length}\n")
+
+
+def list_runs(ctx, seq, min_len, directions="both", versus=None, strand="+"):
+    """[(strand, runs)] of seq against versus, or against itself (then without the trivial diagonal and with one run of each
+    mirror pair: prf_native.unique_runs), one entry per strand of "+", "-" or "both"."""
+    import prf_native
+    out = []
+    for s in "+-":
+        if strand in (s, "both"):
+            runs = ctx.dotpair_runs(seq, seq if versus is None else versus, s, directions, min_len)
+            out.append((s, prf_native.unique_runs(runs, s) if versus is None else runs))
+    return out
+
+
+def no_image(args):
+    """--runs-tsv without -o: the list is all that is asked for."""
+    return args.runs_tsv is not None and args.output_path is None
+
+
 def build_parser():
     """The reference's options and positionals (names as there, so that its command lines run unchanged), plus --block / --tsv."""
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("-w", "--image-size", type=float, help="side of the square image, in inches (default: 5/150 inch per cell)")
     p.add_argument("-d", "--output-dir", default=".", help="directory the images go to; created if missing")
-    p.add_argument("-o", "--output-path", default="dot_plot.png", help="file name of the image when there is exactly one input")
+    p.add_argument("-o", "--output-path", help="file name of the image when there is exactly one input (default: dot_plot.png)")
     p.add_argument("-t", "--filter-threshold", type=int, default=3,
                    help="min_diagonal_run of the noise filter, 0 to 64: a cell stays if its diagonal or anti-diagonal run has "
                         "at least this many cells minus one; 2 or less keeps every cell")
@@ -208,6 +238,14 @@ def build_parser():
                    help="-: compare each row's base with the complement of the column's base, so that an inverted repeat is an "
                         "anti-diagonal; both: draw the cells that only the minus strand keeps in a second colour (one pixel per "
                         "cell only: with --block, plot one strand at a time)")
+    p.add_argument("--runs-tsv", metavar="PATH",
+                   help="Write the maximal diagonal and anti-diagonal runs of matching cells as a table: name, a_start, a_end, X's "
+                        "name, b_start, b_end (ends exclusive, forward coordinates on both strands), strand, direction, length. "
+                        "Needs --min-run. Without --versus each repeat is listed once and the trivial diagonal not at all. "
+                        "Without -o no image is drawn, and sequences above 5,000 positions need no --block.")
+    p.add_argument("--min-run", type=int, metavar="L", help="With --runs-tsv: the cells a run must have to be listed.")
+    p.add_argument("--run-directions", choices=["main", "anti", "both"], default="both",
+                   help="With --runs-tsv: list diagonal runs, anti-diagonal runs or both (default).")
     p.add_argument("input_sequence_or_intervals_or_bed_files", nargs="+",
                    help="any mix of literal ACGT sequences, intervals chrom:start_0based-end, and BED files")
     return p
@@ -236,11 +274,15 @@ def resolve_inputs(args, parser):
         parser.error("--tsv writes the block counts: give --block too")
     if args.block is not None and args.strand == "both":
         parser.error("--strand both colours single cells: with --block, plot one strand at a time (--strand + and --strand -)")
+    if args.runs_tsv is not None and args.min_run is None:
+        parser.error("--runs-tsv lists the runs of at least --min-run cells: give --min-run too")
+    if args.min_run is not None and (args.runs_tsv is None or args.min_run < 1):
+        parser.error(f"--min-run is set to {args.min_run}. It goes with --runs-tsv and must be at least 1.")
     inputs = args.input_sequence_or_intervals_or_bed_files
     out, n_intervals, cache = [], 0, {}
     for i, text in enumerate(inputs):
         if not set(text) - set("ACGT"):                               # a literal nucleotide sequence
-            name = args.output_path if len(inputs) == 1 else f"dot_plot_{i + 1:03d}_of_{len(inputs)}.{len(text)}bp_sequence.png"
+            name = (args.output_path or "dot_plot.png") if len(inputs) == 1 else f"dot_plot_{i + 1:03d}_of_{len(inputs)}.{len(text)}bp_sequence.png"
             out.append(("sequence", 0, text, os.path.join(args.output_dir, name)))
             continue
         if "bed" not in text and not (":" in text and "-" in text):
@@ -271,13 +313,13 @@ def resolve_inputs(args, parser):
     if n_intervals:                                                    # (the reference prints this line always, and crashes
         print(f"Loaded {n_intervals:,d} interval(s) from {args.reference_fasta}")   # on it when there were only literals)
     for name, _begin, seq, _path in out:
-        if args.block is None and len(seq) > MAX_MATRIX_POSITIONS:
+        if args.block is None and len(seq) > MAX_MATRIX_POSITIONS and not no_image(args):
             parser.error(f"The input sequence is too long for one pixel per cell ({len(seq):,d} bp > {MAX_MATRIX_POSITIONS:,d}). "
                          f"Use --block B (a multiple of 64) to plot the density instead.")
         if not seq.isalpha() and seq:
             parser.error(f"Error: the sequence of {name} holds characters that are not letters")
-    if args.tsv and len(out) > 1:
-        parser.error("--tsv takes one input sequence")
+    if (args.tsv or args.runs_tsv) and len(out) > 1:
+        parser.error(f"{'--tsv' if args.tsv else '--runs-tsv'} takes one input sequence")
     return out
 
 
@@ -300,7 +342,7 @@ def resolve_versus(args, parser):
             parser.error(f"Error: {e}")
         begin, end = max(0, start - args.padding), end + args.padding
         name, seq = _fetch(parser, args.reference_fasta, {}, chrom, begin, end)
-    if args.block is None and len(seq) > MAX_MATRIX_POSITIONS:
+    if args.block is None and len(seq) > MAX_MATRIX_POSITIONS and not no_image(args):
         parser.error(f"The --versus sequence is too long for one pixel per cell ({len(seq):,d} bp > {MAX_MATRIX_POSITIONS:,d}). "
                      f"Use --block B (a multiple of 64) to plot the density instead.")
     if not seq.isalpha() and seq:
@@ -325,6 +367,15 @@ def main(argv=None, context=None):
         if args.verbose:
             print(f"[{i + 1}/{len(todo)}] {name}: {len(seq):,d} positions")
         columns = seq if versus is None else versus[2]
+        if args.runs_tsv:
+            x_name, x_begin = (name, begin) if versus is None else versus[:2]
+            listed = list_runs(_context(context), seq, args.min_run, args.run_directions, None if versus is None else columns, args.strand)
+            with open(args.runs_tsv, "wt") as f:
+                for strand, runs in listed:
+                    f.writelines(run_lines(name, begin, x_name, x_begin, strand, runs))
+            print(f"Wrote {args.runs_tsv} ({sum(len(runs) for _, runs in listed):,d} runs)")
+            if no_image(args):
+                continue
         if args.block is None:
             matrix = dot_plot_matrix(seq, args.filter_threshold, 2 if args.show_filtered_pixels else 0, context=context,
                                      versus=None if versus is None else columns, strand=args.strand)
@@ -341,7 +392,8 @@ def main(argv=None, context=None):
                 print(f"Wrote {args.tsv}")
         if args.verbose or len(todo) == 1:
             print(f"Wrote {path} ({len(seq):,d} positions)")
-    print(f"{len(todo):,d} dot plot(s) written to {os.path.abspath(args.output_dir)}")
+    if not no_image(args):
+        print(f"{len(todo):,d} dot plot(s) written to {os.path.abspath(args.output_dir)}")
 
 
 if __name__ == "__main__":

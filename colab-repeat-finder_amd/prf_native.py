@@ -122,6 +122,16 @@ DOTPLOT_EXPORTS = ["prf_dotplot_bits", "prf_dotplot_counts", "prf_dotplot_bits_e
 # the entry points of the dot plot of two ranges (include/prf_dotpair.h, which prf.h includes)
 DOTPAIR_EXPORTS = ["prf_dotpair_bits", "prf_dotpair_counts", "prf_dotpair_bits_ex", "prf_dotpair_counts_ex", "prf_dotpair_bits_seq",
                    "prf_dotpair_counts_seq"]
+# the entry points of the list of diagonal runs of that dot plot (include/prf_dotruns.h, which prf.h includes)
+DOTRUNS_EXPORTS = ["prf_dotpair_runs", "prf_dotpair_runs_ex", "prf_dotpair_runs_seq"]
+DOTRUN_DTYPE = [("row", "<u8"), ("col", "<u8"), ("len", "<u8"), ("dir", "<u4"), ("reserved", "<u4")]   # prf_dotrun, 32 bytes
+DOTRUN_MAIN, DOTRUN_ANTI = 1, 2      # prf_dotrun.dir, and the bits of `directions`
+DOTRUN_MAX_ROWS = 1 << 24            # PRF_DOTRUN_MAX_ROWS
+DOTRUN_LONG_ROWS = 1 << 20           # PRF_DOTRUN_LONG_ROWS
+DOTRUN_PROBE = 16                    # PRF_DOTRUN_PROBE
+DOTRUN_FOLLOW = 2048                 # PRF_DOTRUN_FOLLOW
+DOTRUN_DEFAULT_CAPACITY = 1 << 16    # rows the first of the binding's two calls has room for
+DIRECTIONS = {"main": 1, "anti": 2, "both": 3}
 DOT_LAUNCH_CELLS = 1 << 36   # PRF_DOT_LAUNCH_CELLS
 DOT_MAX_CELLS = 1 << 42      # PRF_DOT_MAX_CELLS
 DOT_MAX_RUN = 64             # PRF_DOT_MAX_RUN
@@ -231,6 +241,11 @@ def load_library():
         lib.prf_dotpair_counts_ex.argtypes = on_genome + counts_tail + [ctypes.c_uint64]
         lib.prf_dotpair_bits_seq.argtypes = one_shot + bits_tail
         lib.prf_dotpair_counts_seq.argtypes = one_shot + counts_tail
+        runs_tail = [ctypes.c_uint32] + [ctypes.c_uint64] * 4 + [ctypes.c_uint32, ctypes.c_uint64, vp, ctypes.c_uint64, u64p,
+                                                                 ctypes.POINTER(ScanStats)]   # strand, window, directions, min_len ...
+        lib.prf_dotpair_runs.argtypes = on_genome[:-6] + runs_tail
+        lib.prf_dotpair_runs_ex.argtypes = on_genome[:-6] + runs_tail + [ctypes.c_uint64]
+        lib.prf_dotpair_runs_seq.argtypes = one_shot[:-6] + runs_tail
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
         lib.prf_measure_hbm_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -424,6 +439,68 @@ def _matrix(ctx, target, begin, end, with_stats, period=None, dot=None, versus=N
     return (out, stats) if with_stats else out
 
 
+def _runs(ctx, a_target, a_range, b_target, b_range, strand, directions, min_len, rows, cols, with_stats, launch_cells):
+    """The one path of the dotpair_runs calls: the targets are (genome, contig) pairs of one genome, or two sequences.  Calls once
+    with DOTRUN_DEFAULT_CAPACITY rows of room and once more with the exact number if there were more."""
+    import numpy as np
+    if strand not in STRANDS:
+        raise ValueError(f"strand is {strand!r}. It must be '+' or '-'.")
+    if directions not in DIRECTIONS:
+        raise ValueError(f"directions is {directions!r}. It must be 'main', 'anti' or 'both'.")
+    if isinstance(min_len, bool) or operator.index(min_len) < 1:
+        raise ValueError(f"min_len is set to {min_len}. It must be at least 1.")
+    one_shot = not isinstance(a_target, tuple)
+    if one_shot == isinstance(b_target, tuple):
+        raise ValueError("the two ranges must both be sequences or both lie in a genome")
+    if not one_shot and b_target[0] is not a_target[0]:
+        raise ValueError("the two ranges must lie in the same resident genome")
+    a_where, na, a_end, _a_keep = _matrix_range(a_target, *a_range)
+    b_where, nb, b_end, _b_keep = _matrix_range(b_target, *b_range)
+    win, _ = _dot_window(na, nb, rows, cols, 0, None)
+    args = a_where + (a_range[0], a_end) + b_where + (b_range[0], b_end, STRANDS[strand]) + win + (DIRECTIONS[directions], min_len)
+    if one_shot:
+        fn, head, tail = ctx.lib.prf_dotpair_runs_seq, (ctx._h,), ()
+    else:
+        fn, head, tail = ctx.lib.prf_dotpair_runs_ex, (ctx._h, a_target[0]._h), (launch_cells,)
+    capacity = DOTRUN_DEFAULT_CAPACITY
+    while True:
+        out = np.zeros(max(1, capacity), dtype=DOTRUN_DTYPE)
+        n, stats = ctypes.c_uint64(0), ScanStats()
+        _check(ctx.lib, fn(*head, *args, out.ctypes.data_as(ctypes.c_void_p), capacity, ctypes.byref(n), ctypes.byref(stats), *tail))
+        if n.value <= capacity:
+            break
+        if n.value > DOTRUN_MAX_ROWS:
+            raise PrfError(PRF_EUNSUPPORTED, f"{n.value} runs are more than one call returns ({DOTRUN_MAX_ROWS}): ask for a larger "
+                                             "min_len or for smaller windows")
+        capacity = n.value
+    runs = out[:n.value][["row", "col", "len", "dir"]].copy()
+    return (runs, stats) if with_stats else runs
+
+
+def run_cells(runs, na, nb):
+    """bool[na, nb]: the cells of a list of runs (fields row, col, len, dir; dir 1: (row + s, col + s), 2: (row + s, col - s))."""
+    import numpy as np
+    out = np.zeros((na, nb), dtype=bool)
+    length = runs["len"].astype(np.int64)
+    which = np.repeat(np.arange(len(runs)), length)                            # the run of every cell
+    s = np.arange(int(length.sum()), dtype=np.int64) - np.repeat(np.cumsum(length) - length, length)
+    step = np.where(runs["dir"] == DOTRUN_MAIN, 1, -1).astype(np.int64)
+    out[runs["row"].astype(np.int64)[which] + s, runs["col"].astype(np.int64)[which] + step[which] * s] = True
+    return out
+
+
+def unique_runs(runs, strand="+"):
+    """The runs of a range compared with ITSELF, each repeat once: raw is symmetric there on both strands, so every run has a
+    mirror image across the main diagonal.  Drops the trivial run (row == col, main, on the plus strand); of each mirror pair of
+    main runs keeps the one with col > row; of each mirror pair of anti runs -- the mirror of (i, j, L) is (j - L + 1, i + L - 1,
+    L) -- keeps the one with row <= col - len + 1, so that a run that is its own mirror stays."""
+    import numpy as np
+    row, col, length = (runs[f].astype(np.int64) for f in ("row", "col", "len"))
+    main = runs["dir"] == DOTRUN_MAIN
+    keep = np.where(main, col > row if strand == "+" else col >= row, row <= col - length + 1)
+    return runs[keep]
+
+
 class Genome:
     """Contigs packed and resident in HBM (prf_genome)."""
 
@@ -471,6 +548,15 @@ class Genome:
         uint32[ceil(rows / block), ceil(columns / block)]."""
         return _matrix(self.ctx, (self, a[0]), a[1], a[2], with_stats, dot=(min_diagonal_run, block, rows, cols, launch_cells),
                        versus=((self, b[0]), b[1], b[2], strand))
+
+    def dotpair_runs(self, a, b, strand="+", directions="both", min_len=DOTRUN_PROBE, rows=None, cols=None, with_stats=False,
+                     launch_cells=0):
+        """The maximal diagonal ("main": cells (row + s, col + s)) and anti-diagonal ("anti": (row + s, col - s)) runs of matching
+        cells of the dot plot of dotpair_bits whose start cell (the one with the smallest row) lies in the window rows x cols and
+        that have at least min_len cells (prf_dotpair_runs): a numpy structured array with the fields row, col, len, dir (1 main,
+        2 anti), sorted by (row, col, dir).  len is never clipped by the window: the lists of a partition into windows add up to
+        the whole list.  run_cells() rasterises a list; unique_runs() halves the list of a range against itself."""
+        return _runs(self.ctx, (self, a[0]), a[1:], (self, b[0]), b[1:], strand, directions, min_len, rows, cols, with_stats, launch_cells)
 
     @property
     def positions(self):
@@ -664,6 +750,11 @@ class Context:
         """Genome.dotpair_counts for two sequences in one call (prf_dotpair_counts_seq)."""
         return _matrix(self, seq_a, a[0], a[1], with_stats, dot=(min_diagonal_run, block, rows, cols, 0),
                        versus=(seq_b, b[0], b[1], strand))
+
+    def dotpair_runs(self, seq_a, seq_b, strand="+", directions="both", min_len=DOTRUN_PROBE, a=(0, None), b=(0, None), rows=None,
+                     cols=None, with_stats=False):
+        """Genome.dotpair_runs for two sequences (str or bytes) in one call: load, list, free (prf_dotpair_runs_seq)."""
+        return _runs(self, seq_a, a, seq_b, b, strand, directions, min_len, rows, cols, with_stats, 0)
 
     def period_counts(self, seq, kmin, kmax, window, begin=0, end=None, with_stats=False):
         """Genome.period_counts for one sequence (str or bytes) in one call: load, count, free (prf_period_counts_seq)."""

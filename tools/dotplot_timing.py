@@ -7,6 +7,10 @@ the launches of several calls after a warm-up (median, minimum, maximum) and cel
 one that takes too long ends alone and nothing is started behind it.  A window that the sequence would clip is refused.
 The pair cases (prf_dotpair_counts / prf_dotpair_bits) are the four smaller self cases as calls of two ranges: A = B =
 the contig, the same window, on the plus and on the minus strand; a fourth field of a case names the strand.
+The runs cases (prf_dotpair_runs; the third field is min_len) count the runs of both directions that start in the same
+2^16 x 2^16 window at min_len 11 and 32 on either strand, and -- runs-self -- all runs of 2^22 positions against themselves at
+min_len 64, four calls of 2^20 rows each (a call takes at most 2^42 cells), which sends the trivial diagonal through the long
+kernel.  They are counting calls (no destination): the time is the kernels', whatever the number of runs.
 
     python3 tools/dotplot_timing.py [--length 50818468] [--runs 7] [--warmup 2] [--limit 300] [--only counts:16:3,bits:14:3:-,...]
 """
@@ -24,7 +28,43 @@ CASES = [("counts", 16, 3), ("counts", 16, 12), ("counts", 16, 64), ("counts", 2
          ("bits", 14, 12)]
 PAIR_CASES = [(mode, log2, t, strand) for strand in "+-" for mode, log2, t in CASES if (mode, log2, t) in
               (("counts", 16, 3), ("counts", 16, 12), ("bits", 14, 3), ("bits", 14, 12))]
+RUNS_CASES = [("runs", 16, 11, "+"), ("runs", 16, 11, "-"), ("runs", 16, 32, "+"), ("runs", 16, 32, "-"), ("runs-self", 22, 64, "+")]
 OFFSET = 30_000_000      # the window's first row and column: in the sequence, behind the stand-in's inner gap of N
+
+
+def count_runs(genome, a, b, strand, min_len, rows, cols):
+    """(runs, ScanStats) of one counting call of prf_dotpair_runs: both directions, no destination."""
+    import ctypes
+    import prf_native
+    n, stats = ctypes.c_uint64(0), prf_native.ScanStats()
+    lib = genome.ctx.lib
+    prf_native._check(lib, lib.prf_dotpair_runs(genome.ctx._h, genome._h, a[0], a[1], a[2], b[0], b[1], b[2], prf_native.STRANDS[strand],
+                                                rows[0], rows[1], cols[0], cols[1], 3, min_len, None, 0, ctypes.byref(n), ctypes.byref(stats)))
+    return n.value, stats
+
+
+def one_runs(args, genome, mode, side, min_len, strand):
+    """The runs cases: the 2^16 window of the whole contig against itself, or a range of `side` positions against itself in
+    calls of 2^20 rows."""
+    whole = (0, 0, (1 << 64) - 1)
+    if mode == "runs":
+        a, windows = whole, [((OFFSET, OFFSET + side), (OFFSET, OFFSET + side))]
+    else:
+        a, windows = (0, OFFSET, OFFSET + side), [((r, r + (1 << 20)), (0, side)) for r in range(0, side, 1 << 20)]
+    # a pass over 2^44 cells takes seconds: one warm-up and three timed passes there
+    warmup, timed = (args.warmup, args.runs) if mode == "runs" else (min(args.warmup, 1), min(args.runs, 3))
+    ms = []
+    for i in range(warmup + timed):
+        total_ms, launches, runs = 0.0, 0, 0
+        for rows, cols in windows:
+            n, stats = count_runs(genome, a, a, strand, min_len, rows, cols)
+            total_ms, launches, runs = total_ms + stats.scan_ms, launches + stats.n_launches, runs + n
+        if i >= warmup:
+            ms.append(total_ms)
+    med = statistics.median(ms)
+    print(json.dumps({"mode": mode, "strand": strand, "rows": side, "cols": side, "min_len": min_len, "runs": timed, "calls": len(windows),
+                      "launches": launches, "scan_ms_median": round(med, 4), "scan_ms_min": round(min(ms), 4), "scan_ms_max": round(max(ms), 4),
+                      "cells_per_s": round(side * side / med * 1e3, 0), "n_runs": runs}), flush=True)
 
 
 def one(args):
@@ -36,6 +76,11 @@ def one(args):
         raise SystemExit(f"--length {args.length} is too short for a window of {side} positions from {OFFSET}")
     ctx = prf_native.Context(0)
     genome = ctx.standin([args.length], [args.seed], 64)
+    if mode.startswith("runs"):
+        one_runs(args, genome, mode, side, t, strand)
+        genome.free()
+        ctx.close()
+        return
     window = (OFFSET, OFFSET + side)
     ms, launches, total = [], 0, 0
     for i in range(args.warmup + args.runs):
@@ -72,7 +117,7 @@ def main():
     args = ap.parse_args()
     if args.case:
         return one(args)
-    for case in [":".join(str(v) for v in c) for c in CASES + PAIR_CASES]:
+    for case in [":".join(str(v) for v in c) for c in CASES + PAIR_CASES + RUNS_CASES]:
         mode, log2, t = case.split(":")[:3]
         if args.only and case not in args.only.split(","):
             continue
