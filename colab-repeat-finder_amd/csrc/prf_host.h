@@ -44,9 +44,11 @@ hipError_t prf_launch_hbm_read(hipStream_t s, const void *p, u64 bytes, u32 *sin
 hipError_t prf_launch_pack_rows(hipStream_t s, const prf_hit_dev *rows, u64 n, const u64 *contig_base, u64 *dst, u64 cap, u64 side_cap,
                                 u64 *side_cnt, u64 *host_word);
 
-// the same with the row count read on the device (behind a scan that is still in flight); side_cnt must be zero and is zero again afterwards
-hipError_t prf_launch_pack_rows_dev(hipStream_t s, const prf_hit_dev *rows, const u64 *n_ptr, u64 cap, const u64 *contig_base, u64 *dst,
-                                    u64 side_cap, u64 *side_cnt);
+// the same with the row count read on the device (behind a scan that is still in flight); side_cnt must be zero and is zero again afterwards.
+// counters: the base of the scan's counter block; rows_cap, slab_cap: the row array and the slabs the scan was launched with -- a scan
+// that overflowed either leaves the all-ones count word, and no row beyond rows_cap is read
+hipError_t prf_launch_pack_rows_dev(hipStream_t s, const prf_hit_dev *rows, const u64 *counters, u64 rows_cap, u64 slab_cap, u64 cap,
+                                    const u64 *contig_base, u64 *dst, u64 side_cap, u64 *side_cnt);
 
 // literal lane (scan_literal.hip): upper-case in place + first non-letter; one thread per (position, motif size) event
 hipError_t prf_launch_lit_upper(hipStream_t s, uint8_t *seq, u64 n, u64 *bad_pos);

@@ -596,7 +596,7 @@ int prf_scan_genome_async_packed(prf_ctx *c, const prf_genome *g, uint32_t kmin,
         const prf_hit_dev *rows = nullptr;
         const int rc = scan_async_impl(c, g, kmin, kmax, min_repeats, min_span, seq_out, &counters, &rows);
         if (rc) return rc;
-        const hipError_t e = prf_launch_pack_rows_dev(c->stream, rows, counters + PRF_CNT_ROWS, capacity_rows, g->d_base,
+        const hipError_t e = prf_launch_pack_rows_dev(c->stream, rows, counters, c->hit_cap, c->slab_cap, capacity_rows, g->d_base,
                                                       (u64 *)dst_device, side_capacity, c->d_side_cnt);
         if (e == hipSuccess) return PRF_OK;
         (void)retire_slot(c, *slot_of(c, *seq_out), true);
@@ -611,8 +611,15 @@ int prf_scan_wait(prf_ctx *c, uint64_t seq, prf_scan_stats *stats) {
     const int rc = retire_slot(c, *sl, false);
     if (rc) return rc;
     const pass_result r = read_fused(sl->h);
-    if (sl->h[PRF_CNT_HIT_OVF] > c->slab_cap || r.nhits > c->hit_cap || sl->h[PRF_CNT_LONG_OVF])
-        return fail(PRF_EUNSUPPORTED, "prf_scan_wait: the buffers sized by the last synchronous scan overflowed; scan synchronously");
+    // (the conditions under which prf_pack_finish_dev_kernel poisons the count word: the wire buffer and this call agree)
+    if (sl->h[PRF_CNT_HIT_OVF] > c->slab_cap)
+        return fail(PRF_EUNSUPPORTED, "prf_scan_wait: the slabs sized by the last synchronous scan overflowed (a tile holds %llu rows, a slab %u); scan synchronously",
+                    (unsigned long long)sl->h[PRF_CNT_HIT_OVF], c->slab_cap);
+    if (r.nhits > c->hit_cap)
+        return fail(PRF_EUNSUPPORTED, "prf_scan_wait: the row array sized by the last synchronous scan overflowed (%llu rows, it holds %llu); scan synchronously",
+                    (unsigned long long)r.nhits, (unsigned long long)c->hit_cap);
+    if (sl->h[PRF_CNT_LONG_OVF])
+        return fail(PRF_EUNSUPPORTED, "prf_scan_wait: a tile's list of long rows overflowed; scan synchronously");
     c->last = {sl->rows, r.nhits, sl->kmax};
     if (stats) fill_stats(stats, r, 1, sl->positions, sl->tiles, seq);
     return PRF_OK;

@@ -93,13 +93,18 @@ __global__ void prf_pack_finish_kernel(u64 *side_cnt, u64 n, u64 *count_word, u6
 }
 
 // The same behind a scan that is still running (prf_scan_genome_async_packed): the row count is not known on the host, the
-// kernels read it from the scan's counter block; a count beyond the buffer's capacity becomes a poisoned count word.
-__global__ __launch_bounds__(256) void prf_pack_rows_dev_kernel(const prf_hit_dev *__restrict__ rows, const u64 *__restrict__ n_ptr,
-                                                                const u64 *__restrict__ contig_base, u64 *__restrict__ dst, u64 cap, u64 side_cap,
-                                                                u64 *__restrict__ side_cnt) {
-    const u64 n = *n_ptr;
+// kernels read it from the scan's counter block (`counters`: its base, as the scan kernel and the gather got it).  The scan's row
+// array holds rows_cap rows, whatever the count says.  A count beyond the buffer's capacity, and a scan that overflowed the
+// buffers it was sized for (the row array, a slab, a tile's list of long rows: what prf_scan_wait tests on the host), become a
+// poisoned count word.
+__global__ __launch_bounds__(256) void prf_pack_rows_dev_kernel(const prf_hit_dev *__restrict__ rows, const u64 *__restrict__ counters,
+                                                                u64 rows_cap, const u64 *__restrict__ contig_base, u64 *__restrict__ dst, u64 cap,
+                                                                u64 side_cap, u64 *__restrict__ side_cnt) {
+    u64 n = counters[PRF_CNT_ROWS];
+    if (n > cap) n = cap;
+    if (n > rows_cap) n = rows_cap;
     const u64 stride = (u64)gridDim.x * blockDim.x;
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n && i < cap; i += stride) {
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const prf_hit_dev h = rows[i];
         const u64 gpos = contig_base[h.contig] + h.start, span = h.end - h.start;
         const u64 s16 = span < 65535ull ? span : 65535ull;
@@ -115,18 +120,21 @@ __global__ __launch_bounds__(256) void prf_pack_rows_dev_kernel(const prf_hit_de
         }
     }
 }
-__global__ void prf_pack_finish_dev_kernel(u64 *side_cnt, const u64 *n_ptr, u64 cap, u64 side_cap, u64 *count_word) {
-    const u64 c = *side_cnt, n = *n_ptr;
-    *count_word = (n > cap || c > side_cap) ? ~0ull : (n | (c << 40));   // all ones: the buffer was too small (multi_gpu.unpack_rows raises)
+__global__ void prf_pack_finish_dev_kernel(u64 *side_cnt, const u64 *counters, u64 rows_cap, u64 slab_cap, u64 cap, u64 side_cap,
+                                           u64 *count_word) {
+    const u64 c = *side_cnt, n = counters[PRF_CNT_ROWS];
+    // all ones: the buffer was too small, or the scan overflowed its own buffers (multi_gpu.unpack_rows raises)
+    const bool bad = n > cap || c > side_cap || n > rows_cap || counters[PRF_CNT_HIT_OVF] > slab_cap || counters[PRF_CNT_LONG_OVF] != 0;
+    *count_word = bad ? ~0ull : (n | (c << 40));
     *side_cnt = 0;
 }
 
-hipError_t prf_launch_pack_rows_dev(hipStream_t s, const prf_hit_dev *rows, const u64 *n_ptr, u64 cap, const u64 *contig_base, u64 *dst,
-                                    u64 side_cap, u64 *side_cnt) {
+hipError_t prf_launch_pack_rows_dev(hipStream_t s, const prf_hit_dev *rows, const u64 *counters, u64 rows_cap, u64 slab_cap, u64 cap,
+                                    const u64 *contig_base, u64 *dst, u64 side_cap, u64 *side_cnt) {
     const u64 blocks = (cap + 255) / 256;
-    hipLaunchKernelGGL(prf_pack_rows_dev_kernel, dim3((u32)(blocks < 4096 ? (blocks ? blocks : 1) : 4096)), dim3(256), 0, s, rows, n_ptr, contig_base,
-                       dst, cap, side_cap, side_cnt);
-    hipLaunchKernelGGL(prf_pack_finish_dev_kernel, dim3(1), dim3(1), 0, s, side_cnt, n_ptr, cap, side_cap, dst + cap);
+    hipLaunchKernelGGL(prf_pack_rows_dev_kernel, dim3((u32)(blocks < 4096 ? (blocks ? blocks : 1) : 4096)), dim3(256), 0, s, rows, counters, rows_cap,
+                       contig_base, dst, cap, side_cap, side_cnt);
+    hipLaunchKernelGGL(prf_pack_finish_dev_kernel, dim3(1), dim3(1), 0, s, side_cnt, counters, rows_cap, slab_cap, cap, side_cap, dst + cap);
     return hipGetLastError();
 }
 

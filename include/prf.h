@@ -279,7 +279,10 @@ int prf_last_hits_packed_to_device(prf_ctx *ctx, const prf_genome *g, void *dst_
 /* A pipelined scan (prf_scan_genome_async) whose rows leave in that wire format with no host step in between: the pack
  * kernels run behind the scan on the library's stream and take the row count from the device.  dst_device as above; a scan
  * with more rows than capacity_rows (or more long rows than side_capacity) leaves an all-ones count word, which
- * multi_gpu.unpack_rows() refuses.  Collect the scan with prf_scan_wait() as usual. */
+ * multi_gpu.unpack_rows() refuses.  So does a scan that overflowed the buffers sized by the last synchronous scan (the row
+ * array or a tile's slab: another genome or other parameters than were sized for): the pack reads no row beyond the row array,
+ * and prf_scan_wait() fails with PRF_EUNSUPPORTED for exactly the scans whose count word is all ones for that reason.
+ * Collect the scan with prf_scan_wait() as usual. */
 int prf_scan_genome_async_packed(prf_ctx *ctx, const prf_genome *g, uint32_t kmin, uint32_t kmax, uint32_t min_repeats,
                                  uint32_t min_span, void *dst_device, uint64_t capacity_rows, uint64_t side_capacity,
                                  uint64_t *seq_out);
