@@ -58,8 +58,9 @@ constexpr int REC_CAP = 192;                                  // group-task cand
 constexpr int FLAG_CAP = 960;                                 // (stream, exact task) flags of a tile (one LDS list, 2 bytes each)
 constexpr int SLOW_CAP = 16;                                  // candidates of a tile that leave the LDS window: finished after the others
 constexpr int SMALL_M = 15;                                   // M(k) below this -> exact task
-constexpr int ROW_CAP_LDS = 448;                              // rows of a tile in the LDS list (more: the slab holds the rest, sorted in R1)
-constexpr int SMEM_HDR = 240;                                 // tile context, counters, next-slot words, long ends
+constexpr int QCAP = 112;                                     // rows of a QUARTER of a tile (16384 start positions) in its LDS sublist
+constexpr int ROW_CAP_LDS = 4 * QCAP;                         // the four sublists (a quarter with more rows: the slab holds them, sorted in R1)
+constexpr int SMEM_HDR = 304;                                 // tile context, counters, next-slot words, long ends
 }  // namespace prf_layout
 
 // minimum number of consecutive matching positions of a reportable run: the reference filters

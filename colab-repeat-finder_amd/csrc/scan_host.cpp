@@ -171,10 +171,10 @@ static int launch_fused(prf_ctx *c, const prf_genome *g, const prf_vplan &plan, 
 #ifdef PRF_STAMPS
     {
         static u64 *dbg_buf = nullptr;
-        const size_t nu = (size_t)(1u << 18) * PRF_VMAX_WAVES * 16;  // up to 262144 tiles
+        const size_t nu = (size_t)(1u << 18) * PRF_VMAX_WAVES * PRF_STAMP_SLOTS;  // up to 262144 tiles
         if (!dbg_buf) HIPCHK(hipMalloc((void **)&dbg_buf, nu * sizeof(u64)));
         if (lv.n <= (1u << 18)) {
-            HIPCHK(hipMemsetAsync(dbg_buf, 0, (size_t)lv.n * PRF_VMAX_WAVES * 16 * sizeof(u64), c->stream));
+            HIPCHK(hipMemsetAsync(dbg_buf, 0, (size_t)lv.n * PRF_VMAX_WAVES * PRF_STAMP_SLOTS * sizeof(u64), c->stream));
             a.dbg = dbg_buf;
             c->stamps_buf = dbg_buf;
             c->stamps_n = lv.n;
@@ -281,7 +281,7 @@ static int dump_stamps(prf_ctx *c, const prf_vplan &plan) {
                     plan.tasks[ti].kind, plan.tasks[ti].k0, plan.tasks[ti].valid, plan.tasks[ti].stride);
     if (c->stamps_buf) {
         HIPCHK(hipStreamSynchronize(c->stream));
-        const size_t nu = (size_t)c->stamps_n * PRF_VMAX_WAVES * 16;
+        const size_t nu = (size_t)c->stamps_n * PRF_VMAX_WAVES * PRF_STAMP_SLOTS;
         std::vector<u64> host(nu);
         HIPCHK(hipMemcpy(host.data(), c->stamps_buf, nu * sizeof(u64), hipMemcpyDeviceToHost));
         if (FILE *f = fopen(path, "wb")) { fwrite(host.data(), 8, nu, f); fclose(f); }

@@ -27,6 +27,7 @@ struct prf_vplanes {
 //                                                            long ends (span >= 65535: at most two rows of a tile, Fine and Wilf)
 // Sorted by the low word = by (start, end).  The gather kernel turns them into 24-byte prf_hit_dev rows.
 #define PRF_LONG_PER_TILE 4u
+#define PRF_STAMP_SLOTS 24        // u64 words per (launch slot, wave) of the stamps build's debug buffer (tools/stamps.py)
 
 // everything the fused kernel needs (passed by value)
 struct prf_vscan_args {
@@ -46,7 +47,7 @@ struct prf_vscan_args {
     u32 min_repeats, min_span;
     const uint4 *tile_info;        // [tile]: {contig, 0, contig base lo, hi}
     u64 *counters;                 // this scan's counter block (zero when the kernel starts)
-    u64 *dbg;                      // diagnostic (PRF_STAMPS) builds only; nullptr otherwise
+    u64 *dbg;                      // diagnostic (PRF_STAMPS) builds only; nullptr otherwise: [launch slot][wave][PRF_STAMP_SLOTS]
 #ifdef PRF_DIAG
     u32 skip;                      // PRF_SKIP: phases left out to time the others (diagnostic builds only; read through vscan_skip)
 #endif

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
 
     PRF_STAMP(0);
 #ifdef PRF_STAMPS
-    if (g.dbg && lane == 0) g.dbg[((u64)slot * MAX_WAVES + wave) * 16 + 12] = __builtin_amdgcn_s_memrealtime();  // 100 MHz, chip-wide
+    if (g.dbg && lane == 0) g.dbg[((u64)slot * MAX_WAVES + wave) * PRF_STAMP_SLOTS + 12] = __builtin_amdgcn_s_memrealtime();  // 100 MHz, chip-wide
 #endif
     // ---- 1. stage: the image is in R1 (DMA issued during the previous tile's rows phase, or above); the virtual lanes from
     // the two prefetched slots; a mixed tile's mask of the streams that hold nothing but N ----
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
             }
             nostart[tid] = m;
         }
-        if (tid < 8) cnt[tid] = 0;  // rows, records, flags, ... (the other set is still read by slow waves)
+        if (tid < (int)CNT_N) cnt[tid] = 0;  // rows, records, flags, ... (the other set is still read by slow waves)
         if (tid == 0) {  // the tile's part of the context (the rest was written once, above)
             TileCtx *tcw = reinterpret_cast<TileCtx *>(prf_smem);
             tcw->w0 = tile * PRF_TILE_WORDS - LIN_PRE;
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
             tcw->slab = (prf_glb_u64 *)(g.slabs + (u64)slot * g.slab_cap);
             tcw->tile_base = tile * PRF_TILE;
             tcw->has_lin = 0u;
-            tcw->cnt_off = (u32)HDR_CNT + 32u * parity;
+            tcw->cnt_off = (u32)HDR_CNT + 4u * CNT_N * parity;
         }
     }
     PRF_STAMP(1);
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
     em.cnt = cnt;
     em.lane = lane;
 #ifdef PRF_STAMPS
-    u64 *task_dbg = g.dbg ? g.dbg + ((u64)slot * MAX_WAVES + wave) * 16 : nullptr;
+    u64 *task_dbg = g.dbg ? g.dbg + ((u64)slot * MAX_WAVES + wave) * PRF_STAMP_SLOTS : nullptr;
 #else
     u64 *task_dbg = nullptr;
 #endif
@@ -350,14 +350,21 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
                 }
             });
         }
-        // the row list is padded to its capacity with the largest key: no bounds test per key when the rows are ranked
-        // (rows that the scan's overflow paths have listed already stay; the verification appends behind them)
-        const u32 n0 = cnt[CNT_ROWS];
-        for (u32 i = (u32)tid; i < (u32)ROW_CAP_LDS; i += (u32)NTH)
-            if (i >= n0) keys[i] = 0xFFFFFFFFu;
+        // every sublist is padded to its capacity with the largest key of its quarter: no bounds test per key when the rows are
+        // ranked (rows that the scan's overflow paths have listed already stay; the verification appends behind them)
+        const prf_u32x4 n0 = *(prf_lds_cu4 *)(cnt + CNT_ROWS);
+        for (u32 i = (u32)tid; i < (u32)ROW_CAP_LDS; i += (u32)NTH) {
+            const u32 q = i / (u32)QCAP, j = i - q * (u32)QCAP;
+            const u32 n0q = q == 0u ? n0.x : (q == 1u ? n0.y : (q == 2u ? n0.z : n0.w));
+            if (j >= n0q) keys[i] = quarter_pad(q);
+        }
         if (tid == 0) {
             reinterpret_cast<TileCtx *>(prf_smem)->has_lin = 1u;
-            cnt[CNT_ROWS0] = n0;
+            cnt[CNT_ROWS0] = n0.x;
+            cnt[CNT_ROWS0 + 1u] = n0.y;
+            cnt[CNT_ROWS0 + 2u] = n0.z;
+            cnt[CNT_ROWS0 + 3u] = n0.w;
+            cnt[CNT_OVF0] = cnt[CNT_OVF];
             cnt[CNT_LONG0] = cnt[CNT_LONG];
         }
     }
@@ -387,7 +394,7 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
         n_recs = n_recs < (u32)REC_CAP ? n_recs : (u32)REC_CAP;
         n_flags = n_flags < (u32)FLAG_CAP ? n_flags : (u32)FLAG_CAP;
 #ifdef PRF_STAMPS
-        if (g.dbg && tid == 0) g.dbg[((u64)slot * MAX_WAVES + 0) * 16 + 11] = (u64)n_flags | ((u64)n_recs << 32);  // (wave 0 has three tasks)
+        if (g.dbg && tid == 0) g.dbg[((u64)slot * MAX_WAVES + 0) * PRF_STAMP_SLOTS + 11] = (u64)n_flags | ((u64)n_recs << 32);  // (wave 0 has three tasks)
 #endif
         if (vscan_skip(g) & 2u) n_flags = 0;   // (diagnostic) the flags are listed but not verified
         if (vscan_skip(g) & 4u) n_recs = 0;    // (diagnostic) the same for the records
@@ -412,7 +419,8 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
             } else {
                 // more than the list holds: the tile's rows so far are dropped, the general routine does everything again
                 if (tid == 0) {
-                    cnt[CNT_ROWS] = cnt[CNT_ROWS0];
+                    for (u32 q = 0; q < 4u; q++) cnt[CNT_ROWS + q] = cnt[CNT_ROWS0 + q];
+                    cnt[CNT_OVF] = cnt[CNT_OVF0];
                     cnt[CNT_LONG] = cnt[CNT_LONG0];
                 }
                 __syncthreads();
@@ -426,7 +434,18 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
     const u64 nw = *(prf_lds_u64 *)next_words;  // (one read)
     slot_next = (u32)__builtin_amdgcn_readfirstlane((int)(u32)nw);
     const u32 entry_next = (u32)(nw >> 32);
-    const u32 n_rows = (vscan_skip(g) & 16u) ? 0u : (u32)__builtin_amdgcn_readfirstlane((int)cnt[CNT_ROWS]);  // (diagnostic: rows counted as none)
+    // rows per quarter of the tile (those behind a sublist's capacity included), wave-uniform; the tile's rows are their sum
+    u32 nq0, nq1, nq2, nq3;
+    {
+        const prf_u32x4 c = *(prf_lds_cu4 *)(cnt + CNT_ROWS);
+        const bool none = (vscan_skip(g) & 16u) != 0;  // (diagnostic: rows counted as none)
+        nq0 = none ? 0u : (u32)__builtin_amdgcn_readfirstlane((int)c.x);
+        nq1 = none ? 0u : (u32)__builtin_amdgcn_readfirstlane((int)c.y);
+        nq2 = none ? 0u : (u32)__builtin_amdgcn_readfirstlane((int)c.z);
+        nq3 = none ? 0u : (u32)__builtin_amdgcn_readfirstlane((int)c.w);
+    }
+    const u32 n_rows = nq0 + nq1 + nq2 + nq3;
+    const bool dense = nq0 > (u32)QCAP || nq1 > (u32)QCAP || nq2 > (u32)QCAP || nq3 > (u32)QCAP;  // a sublist is full: rows in the slab
     const u32 n_long = (u32)__builtin_amdgcn_readfirstlane((int)cnt[CNT_LONG]);
     u64 *slab = g.slabs + (u64)slot * g.slab_cap;
     const u32 n_store = n_rows < g.slab_cap ? n_rows : g.slab_cap;
@@ -443,42 +462,65 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
 
     // ---- 4. the tile's rows, sorted by (start, end), into its slab.  Rank of a row = number of rows with a smaller key; keys
     // are distinct ((start, end) pairs never collide between motif sizes).
-    if (n_rows > (u32)ROW_CAP_LDS) {
-        // A dense tile (the reference's golden chr22 BED has tiles of 750 rows): the rows behind the list went to the slab as
-        // they came.  All of them are collected in R1 -- the window is dead -- and ranked there.
+    if (dense) {
+        // A dense tile -- a quarter with more rows than its sublist holds (the reference's golden chr22 BED has tiles of 750
+        // rows): the rows behind the sublists went to the slab, from its first slot on, as they came.  All rows are collected in R1
+        // -- the window is dead -- grouped by quarter: the four counts give every quarter's region, the rows read back from the slab
+        // find their place in it with an LDS add.  A row is ranked against the 16-byte units that overlap its quarter's region:
+        // every key in front of them is smaller; of the neighbours' keys inside them those of the lower quarter are smaller and
+        // are counted, those of the higher one are not.
         constexpr u32 R1_ROWS = R1_BYTES / 8u;
-        static_assert(R1_ROWS % 32u == 0, "padding of the dense-tile key list");
-        if (n_store <= R1_ROWS) {
+        const u32 m0 = nq0 < (u32)QCAP ? nq0 : (u32)QCAP, m1 = nq1 < (u32)QCAP ? nq1 : (u32)QCAP, m2 = nq2 < (u32)QCAP ? nq2 : (u32)QCAP,
+                  m3 = nq3 < (u32)QCAP ? nq3 : (u32)QCAP;
+        const u32 n_ovf = n_rows - (m0 + m1 + m2 + m3);  // (= cnt[CNT_OVF])
+        const u32 s1 = nq0, s2 = nq0 + nq1, s3 = s2 + nq2;  // first row of the quarters' regions
+        auto pick = [](u32 q, u32 a0, u32 a1, u32 a2, u32 a3) -> u32 { return q == 0u ? a0 : (q == 1u ? a1 : (q == 2u ? a2 : a3)); };
+        if (n_rows <= g.slab_cap && n_rows <= R1_ROWS) {
             prf_lds_u32 *k2 = (prf_lds_u32 *)(prf_smem + R1_OFF), *v2 = k2 + R1_ROWS;
+            prf_lds_u32 *fill = cnt + CNT_ROWS0;  // (free from here on) rows placed in each region so far
+            if (tid < 4) fill[tid] = pick((u32)tid, m0, m1, m2, m3);
             for (u32 i = (u32)tid; i < (u32)ROW_CAP_LDS; i += (u32)NTH) {
-                k2[i] = keys[i];
-                v2[i] = keys[ROW_CAP_LDS + i];
+                const u32 q = i / (u32)QCAP, j = i - q * (u32)QCAP;
+                if (j < pick(q, m0, m1, m2, m3)) {
+                    const u32 at = pick(q, 0u, s1, s2, s3) + j;
+                    k2[at] = keys[i];
+                    v2[at] = keys[ROW_CAP_LDS + i];
+                }
             }
-            for (u32 i = (u32)ROW_CAP_LDS + (u32)tid; i < n_store; i += (u32)NTH) {
-                const u64 r = slab[i];
-                k2[i] = (u32)r;
-                v2[i] = (u32)(r >> 32);
-            }
-            for (u32 i = n_store + (u32)tid; i < ((n_store + 31u) & ~31u); i += (u32)NTH) k2[i] = 0xFFFFFFFFu;
             __syncthreads();
+            for (u32 i = (u32)tid; i < n_ovf; i += (u32)NTH) {
+                const u64 r = slab[i];
+                const u32 q = (u32)r >> 30;
+                const u32 at = pick(q, 0u, s1, s2, s3) + atomicAdd((u32 *)(fill + q), 1u);  // (< the region's end: the quarter's count holds these rows)
+                k2[at] = (u32)r;
+                v2[at] = (u32)(r >> 32);
+            }
+            for (u32 i = n_rows + (u32)tid; i < ((n_rows + 3u) & ~3u); i += (u32)NTH) k2[i] = 0xFFFFFFFFu;
+            __syncthreads();  // (the slab's first slots have been read: the ranked rows may go there)
             typedef __attribute__((address_space(3))) const prf_u32x4 prf_lds_ckey4;
             prf_lds_ckey4 *k4 = (prf_lds_ckey4 *)k2;
-            for (u32 r = (u32)tid; r < n_store; r += (u32)NTH) {
+            for (u32 r = (u32)tid; r < n_rows; r += (u32)NTH) {
                 const u32 mine = k2[r], kv = v2[r];
-                u32 rank = 0;
-                for (u32 c0 = 0; 4u * c0 < n_store; c0 += 8u) {
-#pragma unroll
-                    for (u32 j = 0; j < 8u; j++) {
-                        const prf_u32x4 v = k4[c0 + j];
-                        rank += (v.x < mine ? 1u : 0u) + (v.y < mine ? 1u : 0u) + (v.z < mine ? 1u : 0u) + (v.w < mine ? 1u : 0u);
-                    }
+                const u32 q = mine >> 30;
+                const u32 lo = pick(q, 0u, s1, s2, s3), hi = lo + pick(q, nq0, nq1, nq2, nq3);
+                const u32 u_lo = lo >> 2, u_hi = (hi + 3u) >> 2;
+                u32 rank = 4u * u_lo;
+#pragma unroll 4
+                for (u32 u = u_lo; u < u_hi; u++) {
+                    const prf_u32x4 v = k4[u];
+                    rank += (v.x < mine ? 1u : 0u) + (v.y < mine ? 1u : 0u) + (v.z < mine ? 1u : 0u) + (v.w < mine ? 1u : 0u);
                 }
                 slab[rank] = (u64)mine | ((u64)kv << 32);
             }
             __syncthreads();  // R1 is refilled below
         } else {
-            // more rows than R1 holds (no genome does that): the list goes to the slab as it is, the host sorts
-            for (u32 i = (u32)tid; i < (u32)ROW_CAP_LDS && i < n_store; i += (u32)NTH) slab[i] = (u64)keys[i] | ((u64)keys[ROW_CAP_LDS + i] << 32);
+            // more rows than R1 or the slab holds (no genome does the first; the host repeats the scan with larger slabs after the
+            // second): the sublists go to the slab as they are, behind the rows that are there; the host sorts
+            for (u32 i = (u32)tid; i < (u32)ROW_CAP_LDS; i += (u32)NTH) {
+                const u32 q = i / (u32)QCAP, j = i - q * (u32)QCAP;
+                const u32 at = n_ovf + pick(q, 0u, m0, m0 + m1, m0 + m1 + m2) + j;
+                if (j < pick(q, m0, m1, m2, m3) && at < g.slab_cap) slab[at] = (u64)keys[i] | ((u64)keys[ROW_CAP_LDS + i] << 32);
+            }
             unsorted = true;
         }
     }
@@ -488,42 +530,63 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
     if (slot_next < g.n_launch) sr.load(g, entry_next, tid, wave, R1_OFF);
     else sr.clear();
 
-    if (n_rows && n_rows <= (u32)ROW_CAP_LDS) {
-        // P = 256 / n threads per row (a power of two, adjacent lanes): each counts the smaller keys of its share of the
-        // list, the shares are added up across the P lanes.  Dependent LDS round trips are what this phase costs: the row's own
-        // key and motif size and the first 32 keys of the lane's share are ONE batch of reads; the shares are added with DPP
-        // moves, not LDS shuffles.  More than 256 rows: two passes.
-        const u32 lg = n_rows > 128u ? 0u : (n_rows > 64u ? 1u : (n_rows > 32u ? 2u : 3u));
-        const u32 P = 1u << lg, part = (u32)tid & (P - 1u);
-        typedef __attribute__((address_space(3))) const prf_u32x4 prf_lds_ckey4;
-        prf_lds_ckey4 *k4 = (prf_lds_ckey4 *)keys;
-        for (u32 row0 = 0; row0 < n_rows; row0 += (u32)NTH >> lg) {
-            const u32 row = row0 + ((u32)tid >> lg);
-            const u32 r = row < n_rows ? row : 0u;  // (lanes without a row read row 0: harmless)
-            const u32 mine = keys[r];
-            const u32 kv = keys[ROW_CAP_LDS + r];
-            u32 rank = 0;
-            // part p takes the keys 4 p .. 4 p + 3, then 4 P further on, ...: one 16-byte read per four keys, eight reads in flight
-            for (u32 c0 = part; 4u * c0 < n_rows; c0 += 8u * P) {
-                prf_u32x4 v[8];
-#pragma unroll
-                for (u32 j = 0; j < 8u; j++) v[j] = k4[c0 + j * P];
-                // (all eight reads in flight before the first compare: left alone the compiler issues them two at a time)
-                asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
-#pragma unroll
-                for (u32 j = 0; j < 8u; j++) {
-                    rank += v[j].x < mine ? 1u : 0u;  // (keys past the list are 0xFFFFFFFF: never smaller)
-                    rank += v[j].y < mine ? 1u : 0u;
-                    rank += v[j].z < mine ? 1u : 0u;
-                    rank += v[j].w < mine ? 1u : 0u;
+    PRF_RANK_DECL();
+    {
+        // Wave w ranks sublist w: rows of different quarters are never compared, a row's place in the slab is the number of rows
+        // in the lower quarters plus its rank among its own.  P = 1, 2 or 4 adjacent lanes per row (the largest power of two
+        // <= 64 / n; more than four would leave a lane less than one batch): lane `part` of a row reads the 16-byte units part,
+        // part + P, ... of the sublist, four in flight (two at the sublist's tail), and the P shares are added up with DPP moves.  More than 64 rows in
+        // the quarter: two passes.  Dependent LDS round trips are what this phase costs: the row's own key and motif size and the
+        // first batch of keys are ONE batch of reads.
+        // Smaller-than without the carry flag (a compare and an add through vcc stall on each other, one s_nop per key): two keys
+        // of one sublist agree in their top two bits, so the sign of their difference is the answer; v_alignbit shifts it into a
+        // word of verdicts that is counted once per batch.  (Sublists are padded with the largest key of their quarter.)
+        // No read leaves the sublist: a batch starts below its ceil(n / 4) <= QCAP / 4 units and spans at most 4 P of them, and
+        // what follows the last sublist are the motif-size words, which must not be counted.
+        const u32 nq = wave_s == 0 ? nq0 : (wave_s == 1 ? nq1 : (wave_s == 2 ? nq2 : nq3));
+        const u32 below = wave_s == 0 ? 0u : (wave_s == 1 ? nq0 : (wave_s == 2 ? nq0 + nq1 : nq0 + nq1 + nq2));
+        if (nq && !dense) {
+            const u32 lg = nq > 32u ? 0u : (nq > 16u ? 1u : 2u);
+            const u32 P = 1u << lg, part = (u32)lane & (P - 1u);
+            const u32 units = (nq + 3u) >> 2;
+            prf_lds_u32 *sub = keys + (u32)wave_s * (u32)QCAP;
+            typedef __attribute__((address_space(3))) const prf_u32x4 prf_lds_ckey4;
+            prf_lds_ckey4 *k4 = (prf_lds_ckey4 *)sub + part;
+            for (u32 row0 = 0; row0 < nq; row0 += 64u >> lg) {
+                const u32 row = row0 + ((u32)lane >> lg);
+                const u32 r = row < nq ? row : 0u;  // (lanes without a row read row 0: harmless)
+                PRF_RANK_T0();
+                const u32 mine = sub[r];
+                const u32 kv = sub[ROW_CAP_LDS + r];
+                u32 rank = 0;
+                auto batch = [&](u32 u0, auto nc) {  // N reads in flight, then 2 operations per key and one count
+                    constexpr u32 N = (u32)decltype(nc)::value;
+                    prf_u32x4 v[N];
+                    static_for<0, (int)N>([&](auto jc) { v[decltype(jc)::value] = k4[u0 + (u32)decltype(jc)::value * P]; });
+                    // (all reads in flight before the first difference: left alone the compiler issues them two at a time)
+                    if constexpr (N == 4u) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
+                    else asm volatile("" : "+v"(v[0]), "+v"(v[1]));
+                    u32 bits = 0;
+                    static_for<0, (int)N>([&](auto jc) {
+                        constexpr u32 j = (u32)decltype(jc)::value;
+                        bits = __builtin_amdgcn_alignbit(bits, v[j].x - mine, 31);
+                        bits = __builtin_amdgcn_alignbit(bits, v[j].y - mine, 31);
+                        bits = __builtin_amdgcn_alignbit(bits, v[j].z - mine, 31);
+                        bits = __builtin_amdgcn_alignbit(bits, v[j].w - mine, 31);
+                    });
+                    rank += (u32)__builtin_popcount(bits);
+                };
+                for (u32 u0 = 0; u0 < units; u0 += 4u * P) {  // (wave-uniform: scalar branches)
+                    if (units - u0 > 2u * P) batch(u0, std::integral_constant<u32, 4>{});
+                    else batch(u0, std::integral_constant<u32, 2>{});  // (the sublist's tail: one or two reads per lane are left)
                 }
+                // sum over the P adjacent lanes of a row (wave-uniform P): xor 1, xor 2 by quad permutes
+                if (P >= 2u) rank += (u32)__builtin_amdgcn_update_dpp(0, (int)rank, 0xB1, 0xF, 0xF, true);
+                if (P >= 4u) rank += (u32)__builtin_amdgcn_update_dpp(0, (int)rank, 0x4E, 0xF, 0xF, true);
+                PRF_RANK_T1(rank);
+                rank += below;
+                if (row < nq && part == 0 && rank < g.slab_cap && !(vscan_skip(g) & 64u)) slab[rank] = (u64)mine | ((u64)kv << 32);
             }
-            // sum over the P adjacent lanes of a row (wave-uniform P): xor 1, xor 2 by quad permutes; after those all lanes of a
-            // quad agree, so the half-row and row mirrors pair the right partners for 4 and 8
-            if (P >= 2u) rank += (u32)__builtin_amdgcn_update_dpp(0, (int)rank, 0xB1, 0xF, 0xF, true);
-            if (P >= 4u) rank += (u32)__builtin_amdgcn_update_dpp(0, (int)rank, 0x4E, 0xF, 0xF, true);
-            if (P >= 8u) rank += (u32)__builtin_amdgcn_update_dpp(0, (int)rank, 0x141, 0xF, 0xF, true);
-            if (row < n_rows && part == 0 && rank < g.slab_cap && !(vscan_skip(g) & 64u)) slab[rank] = (u64)mine | ((u64)kv << 32);
         }
     }
     if ((u32)tid < n_long && (u32)tid < PRF_LONG_PER_TILE)
@@ -534,8 +597,9 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
         if (n_long > PRF_LONG_PER_TILE) atomicMax(&g.counters[PRF_CNT_LONG_OVF], (u64)n_long);
     }
     PRF_STAMP(7);
+    PRF_RANK_STORE();
 #ifdef PRF_STAMPS
-    if (g.dbg && lane == 0) g.dbg[((u64)slot * MAX_WAVES + wave) * 16 + 13] = __builtin_amdgcn_s_memrealtime();
+    if (g.dbg && lane == 0) g.dbg[((u64)slot * MAX_WAVES + wave) * PRF_STAMP_SLOTS + 13] = __builtin_amdgcn_s_memrealtime();
 #endif
     // (no barrier here: the next round's first barrier separates this tile's reads of the row list from the next tile's writes)
     }

@@ -10,8 +10,8 @@ using prf_layout::REC_CAP; using prf_layout::FLAG_CAP; using prf_layout::SLOW_CA
 constexpr int MAX_WAVES = PRF_VMAX_WAVES;
 constexpr int NTH = 64 * MAX_WAVES;                           // threads per workgroup, always
 using prf_layout::SMALL_M;
-using prf_layout::ROW_CAP_LDS;
-static_assert(ROW_CAP_LDS % 32 == 0, "the rank loop reads the padded key list 32 keys at a time");
+using prf_layout::ROW_CAP_LDS; using prf_layout::QCAP;
+static_assert(QCAP % 16 == 0 && ROW_CAP_LDS == 4 * QCAP, "a wave ranks one sublist in 16-byte reads, batches of up to four per lane, that stay inside it");
 
 // ---- group-task candidate records: [5:0] lane, [14:6] k, [16:15] 1/2/3 = every 1st/2nd/4th group examined,
 // [48:17] stream word (bit b = stream b*64 + lane may hold a candidate) ----
@@ -34,13 +34,18 @@ __device__ __forceinline__ prf_u32x2 make_rec_halves(u32 tag, u32 word) {
 extern __shared__ __attribute__((aligned(16))) unsigned char prf_smem[];
 using prf_layout::SMEM_HDR;
 // header words: 128.. two sets of tile counters used alternately (a set is reset while the other one is still read)
-constexpr int HDR_CNT = 128;       // [parity][8] u32
-constexpr int HDR_NEXT = 192;      // {next launch slot, its entry}
-constexpr int HDR_LONG = 200;      // [PRF_LONG_PER_TILE] u64: true ends of the rows whose span is clipped
-constexpr int HDR_STATS = 232;     // {candidates looked at, of which verified on the spot} by this workgroup so far (thread 0's)
+constexpr int HDR_CNT = 128;       // [parity][CNT_N] u32
+constexpr int HDR_NEXT = 256;      // {next launch slot, its entry}
+constexpr int HDR_LONG = 264;      // [PRF_LONG_PER_TILE] u64: true ends of the rows whose span is clipped
+constexpr int HDR_STATS = 296;     // {candidates looked at, of which verified on the spot} by this workgroup so far (thread 0's)
 static_assert(HDR_LONG + 8 * (int)PRF_LONG_PER_TILE <= HDR_STATS && HDR_STATS + 8 <= SMEM_HDR, "LDS header layout");
-constexpr u32 CNT_ROWS = 0, CNT_RECS = 1, CNT_EARLY = 2, CNT_LONG = 3, CNT_FLAGS = 4, CNT_SLOW = 5,
-              CNT_ROWS0 = 6, CNT_LONG0 = 7;  // rows / long rows listed before the verification began (the scan's overflow paths)
+// CNT_ROWS + q: rows that start in quarter q of the tile (key >> 30), those behind the sublist's QCAP included; CNT_OVF: the latter
+// over all quarters = their slots in the slab.  The tile's row count is the sum of the four.
+constexpr u32 CNT_N = 16, CNT_ROWS = 0, CNT_RECS = 4, CNT_EARLY = 5, CNT_LONG = 6, CNT_FLAGS = 7, CNT_SLOW = 8, CNT_OVF = 9,
+              CNT_ROWS0 = 10, CNT_OVF0 = 14, CNT_LONG0 = 15;  // rows / long rows listed before the verification began (the scan's overflow paths)
+static_assert(HDR_CNT % 16 == 0 && CNT_ROWS % 4 == 0 && HDR_CNT + 2 * 4 * (int)CNT_N <= HDR_NEXT, "the four row counters are one 16-byte read");
+// sublist q is padded with the largest key of its quarter: differences of two keys of a sublist keep their sign
+__device__ __forceinline__ u32 quarter_pad(u32 q) { return ((q + 1u) << 30) - 1u; }
 
 // LDS is addressed through explicit address-space pointers everywhere: a generic pointer that the compiler cannot trace back
 // to prf_smem becomes a flat_load, which is slower and waits on both memory counters.
@@ -60,10 +65,27 @@ typedef __attribute__((address_space(1))) u64 prf_glb_u64;
 #ifdef PRF_STAMPS
 #define PRF_STAMP(i)                                                                                               \
     do {                                                                                                           \
-        if (g.dbg && lane == 0) g.dbg[((u64)slot * MAX_WAVES + wave) * 16 + (i)] = __builtin_amdgcn_s_memtime(); \
+        if (g.dbg && lane == 0) g.dbg[((u64)slot * MAX_WAVES + wave) * PRF_STAMP_SLOTS + (i)] = __builtin_amdgcn_s_memtime(); \
+    } while (0)
+// Slot 16: cycles of the tile's rows phase that the wave spent ranking (key reads, compares, DPP adds), summed over its passes;
+// the staging issue in front of it and the slab stores behind it are outside.  (The asm pins the rank in front of the second stamp.)
+#define PRF_RANK_DECL() u64 rank_cyc = 0, rank_t0 = 0
+#define PRF_RANK_T0() do { rank_t0 = __builtin_amdgcn_s_memtime(); } while (0)
+#define PRF_RANK_T1(v)                                            \
+    do {                                                          \
+        asm volatile("" : "+v"(v));                               \
+        rank_cyc += __builtin_amdgcn_s_memtime() - rank_t0;       \
+    } while (0)
+#define PRF_RANK_STORE()                                                                                    \
+    do {                                                                                                    \
+        if (g.dbg && lane == 0) g.dbg[((u64)slot * MAX_WAVES + wave) * PRF_STAMP_SLOTS + 16] = rank_cyc; \
     } while (0)
 #else
 #define PRF_STAMP(i) do { } while (0)
+#define PRF_RANK_DECL() do { } while (0)
+#define PRF_RANK_T0() do { } while (0)
+#define PRF_RANK_T1(v) do { } while (0)
+#define PRF_RANK_STORE() do { } while (0)
 #endif
 
 // what the verification step needs about the tile; lives at the start of LDS

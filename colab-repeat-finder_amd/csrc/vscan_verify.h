@@ -2,8 +2,8 @@
 // Phase 3 of the fused kernel, candidates -> rows: the general routines over global memory, the lean ones over the LDS
 // window, the list of deferred candidates, the boundary items, and verify_all / verify_general that drive them.
 
-// One row, as 8 bytes (scan_vertical.h): the first ROW_CAP_LDS of a tile into the LDS list, the others straight to the
-// slab behind them (a tile that dense sorts them in R1 at its end).  Sort key: start in the tile (16 bits), then length
+// One row, as 8 bytes (scan_vertical.h): the first QCAP of each quarter of a tile into that quarter's LDS sublist, the others
+// straight to the slab from its first slot on (a tile that dense sorts all of them in R1 at its end).  Sort key: start in the tile (16 bits), then length
 // clipped to 16 bits -- exact, because of the rows that share a start at most one is longer than two motif sizes (two
 // periods on a long common stretch force their gcd, Fine and Wilf).  The true end of a clipped row goes to
 // the tile's short list of long ends.
@@ -19,13 +19,15 @@ __device__ __forceinline__ void emit_row(const TileCtx &tc, u64 a, u64 b, u32 k)
         }
     }
     const u32 key = ((u32)(a - tc.tile_base) << 16) | (span < 65535ull ? (u32)span : 65535u);
-    const u32 i = atomicAdd((u32 *)(cnt + CNT_ROWS), 1u);
-    if (i < (u32)ROW_CAP_LDS) {
-        prf_lds_u32 *keys = (prf_lds_u32 *)(prf_smem + tc.keys_off);
+    const u32 q = key >> 30;  // the quarter of the tile the row starts in: rows of different quarters are never compared
+    const u32 i = atomicAdd((u32 *)(cnt + CNT_ROWS + q), 1u);
+    if (i < (u32)QCAP) {
+        prf_lds_u32 *keys = (prf_lds_u32 *)(prf_smem + tc.keys_off) + q * (u32)QCAP;
         keys[i] = key;
         keys[ROW_CAP_LDS + i] = kv;
-    } else if (i < tc.slab_cap) {
-        tc.slab[i] = (u64)key | ((u64)kv << 32);
+    } else {
+        const u32 j = atomicAdd((u32 *)(cnt + CNT_OVF), 1u);
+        if (j < tc.slab_cap) tc.slab[j] = (u64)key | ((u64)kv << 32);
     }
 }
 
@@ -471,7 +473,7 @@ __device__ __forceinline__ void boundary_general(const TileCtx &tc, u32 k, u32 S
     if (!motif_is_repeat(a, k)) emit_row(tc, a, b, k);
 }
 
-__device__ __forceinline__ prf_lds_u32 *smem_cnt(u32 parity) { return (prf_lds_u32 *)(prf_smem + HDR_CNT) + 8u * parity; }
+__device__ __forceinline__ prf_lds_u32 *smem_cnt(u32 parity) { return (prf_lds_u32 *)(prf_smem + HDR_CNT) + CNT_N * parity; }
 
 // Candidates -> rows, all waves together once the window is staged.
 //  * exact tasks left ONE ballot-compacted list of (stream, task) flags in LDS, dealt to the threads from thread 0 up;

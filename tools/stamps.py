@@ -1,6 +1,6 @@
 """Diagnostic: per-wave phase times of the fused kernel from the PRF_STAMPS build (libprf_stamps.so).
 Usage (GPU box): PRF_LIB=colab-repeat-finder_amd/libprf_stamps.so PRF_STAMPS_OUT=/tmp/st.bin python tools/stamps.py [length]"""
-import os, sys
+import os, re, sys
 import numpy as np
 sys.path.insert(0, 'colab-repeat-finder_amd'); sys.path.insert(0, '.')
 import prf_native, synth
@@ -16,7 +16,9 @@ for _ in range(3):
 _, st = g.scan(1, 50, 3, 9, fetch=False)
 print('kernel ms', st.phase1_ms)
 st_ms_global = st.phase1_ms
-d = np.fromfile(os.environ['PRF_STAMPS_OUT'], dtype=np.uint64).reshape(-1, 4, 16).astype(np.int64)
+# words per (launch slot, wave) of the stamp record: the kernel's own constant
+SLOTS = int(re.search(r'#define PRF_STAMP_SLOTS (\d+)', open('colab-repeat-finder_amd/csrc/scan_vertical.h').read()).group(1))
+d = np.fromfile(os.environ['PRF_STAMPS_OUT'], dtype=np.uint64).reshape(-1, 4, SLOTS).astype(np.int64)
 t0 = d[:, :, 0].min()
 names = ['stage', 'bar1', 'scan', 'bar2', 'verify', 'bar3', 'rows']
 for w in range(4):
@@ -60,6 +62,13 @@ for w in range(4):
     print('wave', w, 'cycles inside the exact-task functions (sum over the wave\'s exact tasks): median', int(np.median(body)))
     print('wave', w, 'cycles in pushes: exact/coarse tasks median %d mean %.0f, group tasks median %d mean %.0f; both, share of the wave\'s tile time %.3f' % (
         int(np.median(pf)), pf.mean(), int(np.median(pg)), pg.mean(), np.median((pf + pg) / np.maximum(1, d[:, w, 7] - d[:, w, 0]))))
+
+# slot 16: cycles inside the rows phase's rank loop (key reads, compares, DPP adds; summed over the passes of a tile)
+for w in range(4):
+    rk = d[:, w, 16]
+    print('wave', w, 'rank loop cycles: median %d mean %.0f p10 %d p90 %d; share of the rows phase %.3f, of the wave\'s tile time %.4f' % (
+        int(np.median(rk)), rk.mean(), int(np.percentile(rk, 10)), int(np.percentile(rk, 90)),
+        np.median(rk / np.maximum(1, d[:, w, 7] - d[:, w, 6])), np.median(rk / np.maximum(1, d[:, w, 7] - d[:, w, 0]))))
 
 # slot utilisation from the chip-wide 100 MHz counter (slots 12 / 13 = workgroup start / end)
 rs = d[:, :, 12].min(axis=1); re = d[:, :, 13].max(axis=1)
