@@ -24,6 +24,8 @@ bool prf_vertical_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vp
     std::vector<Item> items;
     u32 reach = 0;       // furthest row of a lane's extended stream any task reads
     u32 covered_to = 0;  // group chunks cover motif sizes below this
+    // the k = 1 flags of a clean tile come out of the k = 2 task (prf_plan.h); the k = 1 task stays for the mixed tiles
+    const bool derive_k1 = prf_plan_derives_k1(kmin, kmax, min_repeats, min_span);
     for (u32 k = kmin; k <= kmax; k++) {
         const long long M = prf_plan_min_matches(k, min_repeats, min_span);
         if (M < SMALL_M) {
@@ -32,11 +34,20 @@ bool prf_vertical_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vp
             it.t.kind = (unsigned char)M;  // M >= 1 because min_repeats >= 2
             it.t.valid = 1;
             it.t.stride = 1;
+            it.t.pad = 0;
             // measured (stamps build, 6 workgroups per CU, units of 10 cycles): 4.9 k cycles for M <= 6 (one operation per
             // window), 5.4 k for M = 7 .. 9 (two), 6.0 k from M = 10 on (more rows of the next lane)
             // measured on the final kernel (stamps build, 6 workgroups per CU, units of 10 cycles): 6.6 k cycles for the exact form
             // (M <= 6), 4.6 - 5.2 k for groups of 2 rows (M 7 - 10), 4.0 k for groups of 4 (M >= 11)
             it.cost = M <= 8 ? 660u : (M <= 10 ? 520u : 400u);
+            if (derive_k1 && k == 1) {
+                it.t.pad = PRF_TASK_DERIVED;
+                // on a clean tile: a word read back and pushed; mixed tiles are rare.  (Measured on the stamps build: 1.5 k cycles, the
+                // push's LDS round trip and flag stores -- its wave is the slowest by 1.1 k since; pricing it is the next step,
+                // profiles/derived_k1_notes.md section 4)
+                it.cost = 0;
+            }
+            if (derive_k1 && k == 2) it.t.pad = PRF_TASK_RAISES_K1;
             items.push_back(it);
             reach = std::max<u32>(reach, 4 * (((u32)T + (u32)M - 1 + k + 3) / 4) - 1);
         } else if (k >= covered_to) {
@@ -65,6 +76,7 @@ bool prf_vertical_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vp
             it.t.kind = 0;
             it.t.valid = (unsigned char)valid;
             it.t.stride = (unsigned char)stride;
+            it.t.pad = 0;
             // measured (units of 10 cycles): 10.5 k / 5.1 k / 4.2 k cycles with 8 sizes, 2.2 k for stride 4 with 3; a task of four
             // sizes reads three quarters of the rows of one of eight
             // measured: stride 1 with 4 sizes 6.5 k cycles, stride 2 with 8 sizes 8.3 k, stride 4 with 8 / 7 sizes 4.4 - 4.9 k / 4.2 k
@@ -77,10 +89,13 @@ bool prf_vertical_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vp
     }
     if (items.size() > PRF_VMAX_TASKS) return false;
     // longest-processing-time-first assignment to at most 4 waves
-    const u32 nw = std::max<u32>(1, std::min<u32>(PRF_VMAX_WAVES, (u32)items.size()));
+    // (the derived k = 1 task is not dealt: it goes behind the k = 2 task, whose wave hands it the word, below)
+    std::vector<Item> sorted;
+    for (const Item &it : items)
+        if (!(it.t.pad & PRF_TASK_DERIVED)) sorted.push_back(it);
+    const u32 nw = std::max<u32>(1, std::min<u32>(PRF_VMAX_WAVES, (u32)sorted.size()));
     std::vector<std::vector<Item>> bins(nw);
     std::vector<u32> load(nw, 0);
-    std::vector<Item> sorted = items;
     std::stable_sort(sorted.begin(), sorted.end(), [](const Item &a, const Item &b) { return a.cost > b.cost; });
     // The ticket for the workgroup's next launch slot is an atomic whose value the compiler waits for on the spot (~3 k
     // cycles with a thousand workgroups drawing): it is dealt like a task, to the wave with the least other work -- or to
@@ -135,6 +150,31 @@ bool prf_vertical_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vp
         }
         if (!moved) break;
     }
+    // The order inside a wave: group tasks that examine every or every 2nd group first, exact tasks next, stride-4 group tasks
+    // last.  The tile's record list takes 192 records, first come first served, and a record that finds no slot is verified on
+    // the spot by the general routine with one look per examined group of its stream: four looks at stride 1, one at stride 4.
+    // In a tile of clusters (chr22-real's densest tile sets that workload's kernel time; its group tasks have several times 192
+    // records) the slots should therefore go to the small strides.  With the tasks in the order of the deal, the stride-1 task
+    // of k = 8 .. 11 came behind two exact tasks, found the list full and verified alone for 103 k cycles, where the parent's
+    // three waves with stride-4 tasks took 22 - 33 k each; first in its wave but behind two stride-4 tasks of other waves it
+    // still took 75 k (profiles/derived_k1_notes.md).  Only a plan that derives the k = 1 flags is dealt anew and ordered so:
+    // every other plan is what it was.
+    auto rank_of = [](const Item &it) { return it.t.kind != 0 ? 1 : (it.t.stride < 4 ? 0 : 2); };
+    for (auto &bin : bins)
+        if (derive_k1) std::stable_sort(bin.begin(), bin.end(), [&](const Item &a, const Item &b) {
+            if (rank_of(a) != rank_of(b)) return rank_of(a) < rank_of(b);
+            return a.t.kind == 0 && a.t.k0 < b.t.k0;
+        });
+    // the derived k = 1 task directly behind the k = 2 task, in the same wave: on a clean tile it pushes the word that task left
+    // for it in LDS (a wave's LDS operations are carried out in order: no barrier in between)
+    for (const Item &it : items)
+        if (it.t.pad & PRF_TASK_DERIVED)
+            for (auto &bin : bins)
+                for (size_t i = 0; i < bin.size(); i++)
+                    if (bin[i].t.pad & PRF_TASK_RAISES_K1) {
+                        bin.insert(bin.begin() + (long)i + 1, it);
+                        break;
+                    }
     {
         // default: the short, latency-bound phases (stage, the record waves of the verify phase, rows) at priority 2, the scan
         // (long, plenty of independent arithmetic) and the flag waves (they wait at the barrier anyway) at 0.  Measured on
@@ -170,7 +210,6 @@ bool prf_vertical_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vp
         plan->wave_begin[w] = plan->n_tasks;
         for (const Item &it : bins[w]) {
             prf_vtask t = it.t;
-            t.pad = 0;
             t.item0 = 0;
             if (t.kind == 0) {
                 t.item0 = (unsigned short)plan->n_group_k;
@@ -209,8 +248,8 @@ int prf_plan_json(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, char *buf, 
         for (u32 w = 0; w < plan.n_waves; w++)
             for (u32 ti = plan.wave_begin[w]; ti < plan.wave_begin[w + 1]; ti++) {
                 const prf_vtask &t = plan.tasks[ti];
-                snprintf(tmp, sizeof tmp, "%s{\"wave\": %u, \"kind\": %u, \"k0\": %u, \"valid\": %u, \"stride\": %u}", first ? "" : ", ",
-                         w, (unsigned)t.kind, (unsigned)t.k0, (unsigned)t.valid, (unsigned)t.stride);
+                snprintf(tmp, sizeof tmp, "%s{\"wave\": %u, \"kind\": %u, \"k0\": %u, \"valid\": %u, \"stride\": %u, \"derive\": %u}",
+                         first ? "" : ", ", w, (unsigned)t.kind, (unsigned)t.k0, (unsigned)t.valid, (unsigned)t.stride, (unsigned)(t.pad & 3u));
                 out += tmp;
                 first = false;
             }

@@ -16,12 +16,16 @@ typedef unsigned int u32;
 // One unit of scan work for one wave on one tile.
 //  kind 0     : "group" task -- the 8 motif sizes k0 .. k0+7 (k0 % 4 == 0) selected by `valid`, all with M(k) >= 15
 //  kind 1..14 : "exact" task -- the single motif size k0 (<= 14), whose minimum run length M(k0) equals `kind`
+// `pad` of an exact task (prf_plan_derives_k1): the k = 1 flags of a clean tile are the k = 2 task's echoes.
+#define PRF_TASK_DERIVED 1u     // the k = 1 task: a clean tile does not run it (a mixed tile does), it pushes the word left for it
+#define PRF_TASK_RAISES_K1 2u   // the k = 2 task: on a clean tile it leaves its echo starts for the k = 1 task, which the plan puts
+                                // directly behind it in the same wave
 struct alignas(4) prf_vtask {   // (two dwords: the kernel reads a task with one scalar load)
     unsigned short k0;
     unsigned char kind;
     unsigned char valid;
     unsigned char stride;   // group tasks: examine every `stride`-th aligned group of 8 rows (1, 2 or 4)
-    unsigned char pad;
+    unsigned char pad;      // exact tasks: PRF_TASK_* flags; 0 otherwise
     unsigned short item0;   // group tasks: index of the task's first motif size among all motif sizes of group tasks;
                             // exact tasks: index among the exact tasks
 };
@@ -68,6 +72,15 @@ constexpr int SMEM_HDR = 304;                                 // tile context, c
 static inline long long prf_plan_min_matches(u32 k, u32 min_repeats, u32 min_span) {
     const long long a = (long long)(min_repeats - 1) * (long long)k, b = (long long)min_span - (long long)k;
     return a > b ? a : b;
+}
+
+// The k = 1 task's flags of a clean tile can be read off the k = 2 task: a homopolymer run of L >= M(1) matches at
+// distance 1 that starts at position t is a run of L - 1 matches at distance 2 that starts at t, and one whose two letters are
+// equal -- what the k = 2 task's echo test (exact form, M(2) <= 8) finds and throws away.  Every k = 1 start is among those
+// echoes iff M(2) <= M(1) - 1, which is min_span >= 2 min_repeats.
+static inline bool prf_plan_derives_k1(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span) {
+    return kmin == 1 && kmax >= 2 && min_repeats >= 2 && prf_plan_min_matches(2, min_repeats, min_span) <= 8 &&
+           (u64)min_span >= 2ull * min_repeats;
 }
 
 // false if the parameters are outside what the fused kernel takes (-> generic kernel)

@@ -30,7 +30,9 @@
 //      * exact task, one motif size k with M(k) = M <= 8 (compiled per (k, M)): mismatch word per row
 //        (2 operations), sliding OR over exactly M rows; a row whose M successors all match and whose predecessor
 //        does not is the start of a run of >= M.  k = 2, 3, 4 on a clean tile leave out the starts whose run is the
-//        echo of a shorter motif (tested once per segment of start rows, vscan_tasks.h): never a row.
+//        echo of a shorter motif (tested once per segment of start rows, vscan_tasks.h): never a row.  The echoes k = 2
+//        leaves out are the homopolymer starts: where min_span >= 2 min_repeats they ARE the k = 1 task's answer on a
+//        clean tile, and that task is not run there (prf_plan_derives_k1).
 //      * coarse task, one motif size with 9 <= M <= 14: the same on aligned groups of 2 or 4 rows (a run of >= M rows
 //        holds floor((M + 1) / G) - 1 consecutive all-match groups).
 //      * group task, 8 motif sizes k0..k0+7 with M(k) >= 15: a run of >= 15 matches contains an aligned
@@ -297,7 +299,7 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
     {
         u32 allow = hasx ? ~nostart[lane] : ~0u;
         if (vscan_skip(g) & 1u) allow = 0u;  // (diagnostic, PRF_SKIP: no flags, no records)
-        run_tasks<NC>((prf_lds_cu4 *)vimg, hotw, g.plan, wave, lane, hasx, allow, em, task_dbg);
+        run_tasks<NC>((prf_lds_cu4 *)vimg, hotw, nostart, g.plan, wave, lane, hasx, allow, em, task_dbg);  // (nostart: free on a clean tile)
     }
     // ---- 3a. R1 <- the window of the linear planes H and L (tile - 128 .. tile + 65536 + 1536 positions), in 16-byte units: unit
     // u < LW/2 is H's word pair u, the others L's; piece = 64 units = 1 KiB.  R1 is the image until the LAST wave has finished its

@@ -298,9 +298,17 @@ __device__ __forceinline__ u32 window_or(const u32 (&mm)[LM], const u32 (&o3)[LO
 // segment with the one operation per row they cost anyway, and hot |= seg & prim closes the segment: 3 - 5 operations per
 // segment instead of 3 - 4 per row.  A mixed tile suppresses nothing (a not-ACGT position reads as A: the true start may lie
 // where the image sees the middle of a run).  Lane 0's conservative row -1 stays: an echo is never a row, wherever it began.
+// K = 2 keeps what it throws away: its echo starts are the starts of the homopolymer runs, and those are the k = 1 task's
+// answer.  A k = 1 run of L matches from position t (t .. t+L equal, t-1 different) is a k = 2 run of L - 1 matches from the
+// same t (row t-1 fails: t-1 differs from t+1) whose two letters are equal; an echo start of >= M matches at distance 2 is,
+// the other way round, a run of >= M + 1 matches at distance 1 that cannot have begun earlier.  So with M(1) = M(2) + 1 -- which
+// is what min_span >= 2 min_repeats gives (prf_plan_derives_k1) -- hot1 |= seg & ~prim, one more operation per segment, is the
+// word exact_stream<1, M + 1> would return, the conservative row -1 included: the plan then has no clean tile run the k = 1
+// task (run_tasks hands it this word).  On a mixed tile prim is all ones and hot1 empty: there the k = 1 task runs.
+// Returns hot in the low word and, for K = 2, hot1 in the high one.
 // Not inlined: one compact function per (K, M), called by the one wave that runs the task.
 template <int K, int M, int NC>
-__device__ __attribute__((noinline)) u32 exact_stream(prf_lds_cu4 *vimg, int lane, bool relax) {
+__device__ __attribute__((noinline)) u64 exact_stream(prf_lds_cu4 *vimg, int lane, bool relax) {
     constexpr int PS = RG * NC;
     constexpr bool ECHO = K >= 2 && K <= 4;
     constexpr int D = K == 4 ? 2 : 1;                               // K / p
@@ -317,6 +325,7 @@ __device__ __attribute__((noinline)) u32 exact_stream(prf_lds_cu4 *vimg, int lan
     u32 o3[NM + 1];
     u32 hot = 0, prev = 0;  // prev: the window one row earlier
     u32 seg = 0;            // (ECHO) the starts of the current segment
+    u32 hot1 = 0;           // (K = 2) the echo starts: the k = 1 task's word
     u32 prim[ECHO ? T / SEG + 1 : 1];  // (ECHO) prim[j / SEG]: the K letters at row j are no power of a shorter word
     const u32 no_echo = relax ? ~0u : 0u;  // a mixed tile suppresses nothing (wave-uniform)
     auto load_slot = [&](auto gc) {
@@ -379,15 +388,17 @@ __device__ __attribute__((noinline)) u32 exact_stream(prf_lds_cu4 *vimg, int lan
                         }
                         // the segment's last start row (the one that ends at row T stops at T - 1): at most one start in it, and
                         // the sampled row lies inside that start's run
-                        if constexpr (t % SEG == 0 || t == T - 1)
+                        if constexpr (t % SEG == 0 || t == T - 1) {
                             hot = bitop3<(TA | (TB & TC)) & 0xFF>(hot, seg, prim[(t + SEG - 1) / SEG]);  // hot | (seg & prim)
+                            if constexpr (K == 2) hot1 = bitop3<(TA | (TB & ~TC)) & 0xFF>(hot1, seg, prim[(t + SEG - 1) / SEG]);  // hot1 | (seg & ~prim)
+                        }
                     }
                     prev = win;
                 }
             }
         });
     });
-    return hot;
+    return (u64)hot | ((u64)hot1 << 32);
 }
 
 // ---- the same question answered more coarsely for M >= 9: rows in aligned groups of G = 2 (M <= 10) or 4 ----
@@ -493,7 +504,7 @@ constexpr int exact_variant_k(int v) {
     return K;
 }
 template <int LO, int HI, int NC>
-__device__ __forceinline__ u32 exact_dispatch(prf_lds_cu4 *vimg, int lane, bool relax, u32 v) {
+__device__ __forceinline__ u64 exact_dispatch(prf_lds_cu4 *vimg, int lane, bool relax, u32 v) {
     if constexpr (LO == HI) {
         constexpr int K = exact_variant_k(LO), M = K + (LO - exact_variant_of(K, K));
         static_assert(M >= K && M < SMALL_M && exact_variant_of(K, M) == LO, "variant numbering");
@@ -507,16 +518,17 @@ __device__ __forceinline__ u32 exact_dispatch(prf_lds_cu4 *vimg, int lane, bool 
 }
 
 template <int NC>
-__device__ __forceinline__ u32 exact_any(prf_lds_cu4 *vimg, int lane, bool relax, u32 k, u32 M) {
+__device__ __forceinline__ u64 exact_any(prf_lds_cu4 *vimg, int lane, bool relax, u32 k, u32 M) {
     // (min_repeats - 1) * k <= M < SMALL_M and min_repeats >= 2: k <= M
     const u32 v = (k - 1u) * (2u * (u32)SMALL_M - k) / 2u + (M - k);
     return exact_dispatch<0, exact_variants() - 1, NC>(vimg, lane, relax, v);
 }
 
 // relax: mixed tile (see the head of the file); allow = ~(streams of this lane that hold nothing but N), all ones on a clean tile
+// k1w: 64 words of LDS that are free while a clean tile is scanned (the derived k = 1 flags pass through them, see below)
 template <int NC>
-__device__ __forceinline__ void run_tasks(prf_lds_cu4 *vimg, prf_lds_u32 *hotw, const prf_vplan &plan, int wave, int lane, bool relax, u32 allow,
-                                          Emit &em, u64 *dbg) {
+__device__ __forceinline__ void run_tasks(prf_lds_cu4 *vimg, prf_lds_u32 *hotw, prf_lds_u32 *k1w, const prf_vplan &plan, int wave, int lane, bool relax,
+                                          u32 allow, Emit &em, u64 *dbg) {
     const u32 t_end = plan.wave_begin[wave + 1];
     {   // (opaque: the exact tasks are functions, and a callee that knows the image's address as a constant looks the dynamic LDS
         // base up in a table in memory on every call -- handed over as an argument it is a register)
@@ -538,7 +550,7 @@ __device__ __forceinline__ void run_tasks(prf_lds_cu4 *vimg, prf_lds_u32 *hotw, 
         task.kind = (unsigned char)((tw0 >> 16) & 0xFFu);
         task.valid = (unsigned char)(tw0 >> 24);
         task.stride = (unsigned char)(tw1 & 0xFFu);
-        task.pad = 0;
+        task.pad = (unsigned char)((tw1 >> 8) & 0xFFu);
         task.item0 = (unsigned short)(tw1 >> 16);
 #ifdef PRF_STAMPS
         if (dbg && lane == 0 && ti - plan.wave_begin[wave] < 8u) dbg[8 + (ti - plan.wave_begin[wave])] = __builtin_amdgcn_s_memtime();
@@ -553,16 +565,30 @@ __device__ __forceinline__ void run_tasks(prf_lds_cu4 *vimg, prf_lds_u32 *hotw, 
                 else group_task<NC, false, false>(vimg, lane, task.k0, task.valid, task.stride, allow, em);
             }
         } else {
+            // (wave-uniform) a plan that derives the k = 1 flags: on a clean tile the k = 2 task leaves its second word -- its echo
+            // starts, see exact_stream -- in LDS (k1w: the words of the all-N masks, which only a mixed tile has), and the k = 1
+            // task, which the plan puts directly behind it in the same wave, is not run: it pushes that word as its own.  (A second
+            // push inside the k = 2 task kept the word and the task's fields alive across the first one's calls: 2 - 8 more spilled
+            // SGPRs.)  A mixed tile suppresses no echo, so that word is empty there and the k = 1 task runs itself.
+            u32 word;
 #ifdef PRF_STAMPS
             const u64 tc0 = __builtin_amdgcn_s_memtime();
-            const u32 word = exact_any<NC>(vimg, lane, relax, task.k0, task.kind);
+#endif
+            if ((task.pad & PRF_TASK_DERIVED) && !relax) {
+                word = k1w[lane];
+            } else {
+                const u64 words = exact_any<NC>(vimg, lane, relax, task.k0, task.kind);
+                word = (u32)words & allow;
+                if ((task.pad & PRF_TASK_RAISES_K1) && !relax) k1w[lane] = (u32)(words >> 32) & allow;
+            }
+#ifdef PRF_STAMPS
             asm volatile("" ::"v"(word));
             const u64 tc1 = __builtin_amdgcn_s_memtime();
             t_call += tc1 - tc0;
-            em.push_flags(word & allow, task.item0, task.k0, hotw);
+#endif
+            em.push_flags(word, task.item0, task.k0, hotw);
+#ifdef PRF_STAMPS
             em.t_push_f += __builtin_amdgcn_s_memtime() - tc1;
-#else
-            em.push_flags(exact_any<NC>(vimg, lane, relax, task.k0, task.kind) & allow, task.item0, task.k0, hotw);
 #endif
         }
     }
