@@ -14,8 +14,105 @@ using namespace prf_layout;
 static constexpr int MAX_WAVES = PRF_VMAX_WAVES;
 
 // ---------------------------------------------------------------------------------------------------
+// What a task costs the wave that runs it, in cycles per tile: the median from a task's stamp to the next one's, the push of its
+// answers included, on the default workload's stand-in at six workgroups per CU (make STAMPS=1, tools/stamps.py 400000000
+// standin2; profiles/scan_handover/stamps_parent_*.txt: seven runs that agree within 60 cycles per task).  Measured are the
+// thirteen tasks of the default plan; the rest of the table is carried over from them and says so.  A wave's first task costs
+// about 300 cycles more than the same task later (k = 3: 4 340 first, 4 032 second): every wave has one first task, so that is
+// a constant of the wave (FIRST_TASK), taken off the figures of the four tasks that were measured as first ones.
+namespace {
+constexpr u32 FIRST_TASK = 300;
+constexpr u32 K1_HANDOVER = 1660;  // the derived k = 1 task on a clean tile: a word read back from LDS and pushed (1 656 - 1 664)
+
+u32 task_price(const prf_vtask &t) {
+    if (t.kind != 0) {
+        if (t.pad & PRF_TASK_DERIVED) return K1_HANDOVER;
+        const u32 k = t.k0, M = t.kind;
+        if (M <= 8) {
+            // the exact form, per (k, M): (2, 7) 3 988 - 4 016, (3, 6) 4 340 - 4 348 as a first task, (4, 8) 4 256 - 4 268 as a first
+            // task; the classes that were not measured read as many slots of rows as these (10 or 11) and are priced alike
+            if (k == 2 && M == 7) return 4000;
+            if (k == 3 && M == 6) return 4040;
+            if (k == 4 && M == 8) return 3960;
+            return 4000;
+        }
+        // the coarse form: groups of 2 rows for M = 9, 10 ((5, 10): 3 632 - 3 636), of 4 from M = 11 on ((6, 12): 3 740 - 3 756 in the
+        // middle of its wave, (7, 14): 3 436 - 3 448 as its wave's last task)
+        return M <= 10 ? 3630 : 3600;
+    }
+    // group tasks, by stride and number of sizes.  Measured: stride 1 with 4 sizes 4 940 - 4 956 as a first task, stride 2 with 8
+    // sizes 5 448 - 5 456 as a first task, stride 4 with 8 sizes 3 636 - 3 708 (three tasks), with 7 sizes 3 576 - 3 624.  A size more
+    // or less is worth 100 cycles at stride 4, where one block of rows is examined; the slopes of the strides 2 and 1 (two and
+    // four blocks) are that times the blocks and are NOT measured: the default plan has one task of each.
+    const u32 n = (u32)__builtin_popcount((unsigned)t.valid);
+    if (t.stride == 1) return 3050 + 400 * n;
+    if (t.stride == 2) return 3550 + 200 * n;
+    return 2900 + 100 * n;
+}
+
+// What the deal minimises.  The first two waves to leave the scan load the verify window, and their wait for the slowest wave
+// hides that load: with the waves' loads sorted a1 <= a2 <= a3 <= a4 the verify phase can begin at max(a4, a2 + W'), W' being the
+// time from the second wave's arrival to its window data being in registers less the code that follows the last arrival anyway
+// (its arrival atomic and the barrier).  Measured (profiles/scan_handover_notes.md): W' = 1.35 k cycles -- and a deal that
+// respects it buys nothing on any workload (the wait of one workgroup is issue time for the five others), while the one it
+// picks for the default parameters costs chr22-real, whose kernel time is its densest tile, 9 % by the order in which the
+// group tasks reach the record list.  So W' is 0 in the product: plain levelling.  A wave without tasks has load 0.
+#ifdef PRF_DIAG
+const u32 WINDOW_W = getenv("PRF_PLAN_W") ? (u32)strtoul(getenv("PRF_PLAN_W"), nullptr, 0) : 0u;  // (diagnostic: sweep)
+#else
+constexpr u32 WINDOW_W = 0;
+#endif
+
+constexpr u32 PRIO_HANDOVER = 3, PRIO_FLAGS = 2;  // (prf_vplan::prio, the fields << 12 and << 6: the best of the sweep, see prio_cfg below)
+
+struct DealKey {  // smaller is better: the objective, then the busiest wave, then the sum of the two busiest
+    u32 obj, a4, a34;
+    bool operator<(const DealKey &o) const { return obj != o.obj ? obj < o.obj : (a4 != o.a4 ? a4 < o.a4 : a34 < o.a34); }
+};
+DealKey deal_key(const u32 (&load)[PRF_VMAX_WAVES]) {
+    u32 a[PRF_VMAX_WAVES];
+    std::copy(load, load + PRF_VMAX_WAVES, a);
+    std::sort(a, a + PRF_VMAX_WAVES);
+    return DealKey{std::max(a[PRF_VMAX_WAVES - 1], a[1] + WINDOW_W), a[PRF_VMAX_WAVES - 1], a[PRF_VMAX_WAVES - 1] + a[PRF_VMAX_WAVES - 2]};
+}
+
+// Every deal of a dozen tasks can be looked at: depth first over the tasks in order of falling cost, a task into each wave whose
+// load differs from that of the waves tried before it (equal loads give the same deals), a branch given up when what is dealt
+// already does no better than the best complete deal -- the loads only grow, and with them a4 and a2.  `best` comes in as the
+// local search's deal, so the bound bites from the start.  The count of nodes is capped: a plan with more tasks than that
+// allows keeps the best deal seen.
+struct DealSearch {
+    const std::vector<u32> &cost;
+    std::vector<u32> where, best_where;
+    u32 load[PRF_VMAX_WAVES] = {};
+    DealKey best;
+    long nodes = 0;
+    static constexpr long MAX_NODES = 400000;
+    void go(size_t i) {
+        if (++nodes > MAX_NODES) return;
+        const DealKey here = deal_key(load);
+        if (!(here < best)) return;
+        if (i == cost.size()) {
+            best = here;
+            best_where = where;
+            return;
+        }
+        for (u32 w = 0; w < (u32)PRF_VMAX_WAVES; w++) {
+            bool seen = false;
+            for (u32 v = 0; v < w; v++) seen = seen || load[v] == load[w];
+            if (seen) continue;
+            load[w] += cost[i];
+            where[i] = w;
+            go(i + 1);
+            load[w] -= cost[i];
+        }
+    }
+};
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------
 // Work plan: which wave runs which motif sizes.  Pure host code.
-bool prf_vertical_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vplan *plan) {
+static bool build_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vplan *plan) {
     if (kmin < 1 || kmax < kmin || kmax > PRF_VMAX_K || min_repeats < 2) return false;
     struct Item {
         prf_vtask t;
@@ -35,19 +132,9 @@ bool prf_vertical_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vp
             it.t.valid = 1;
             it.t.stride = 1;
             it.t.pad = 0;
-            // measured (stamps build, 6 workgroups per CU, units of 10 cycles): 4.9 k cycles for M <= 6 (one operation per
-            // window), 5.4 k for M = 7 .. 9 (two), 6.0 k from M = 10 on (more rows of the next lane)
-            // measured on the final kernel (stamps build, 6 workgroups per CU, units of 10 cycles): 6.6 k cycles for the exact form
-            // (M <= 6), 4.6 - 5.2 k for groups of 2 rows (M 7 - 10), 4.0 k for groups of 4 (M >= 11)
-            it.cost = M <= 8 ? 660u : (M <= 10 ? 520u : 400u);
-            if (derive_k1 && k == 1) {
-                it.t.pad = PRF_TASK_DERIVED;
-                // on a clean tile: a word read back and pushed; mixed tiles are rare.  (Measured on the stamps build: 1.5 k cycles, the
-                // push's LDS round trip and flag stores -- its wave is the slowest by 1.1 k since; pricing it is the next step,
-                // profiles/derived_k1_notes.md section 4)
-                it.cost = 0;
-            }
+            if (derive_k1 && k == 1) it.t.pad = PRF_TASK_DERIVED;
             if (derive_k1 && k == 2) it.t.pad = PRF_TASK_RAISES_K1;
+            it.cost = task_price(it.t);
             items.push_back(it);
             reach = std::max<u32>(reach, 4 * (((u32)T + (u32)M - 1 + k + 3) / 4) - 1);
         } else if (k >= covered_to) {
@@ -77,79 +164,93 @@ bool prf_vertical_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vp
             it.t.valid = (unsigned char)valid;
             it.t.stride = (unsigned char)stride;
             it.t.pad = 0;
-            // measured (units of 10 cycles): 10.5 k / 5.1 k / 4.2 k cycles with 8 sizes, 2.2 k for stride 4 with 3; a task of four
-            // sizes reads three quarters of the rows of one of eight
-            // measured: stride 1 with 4 sizes 6.5 k cycles, stride 2 with 8 sizes 8.3 k, stride 4 with 8 / 7 sizes 4.4 - 4.9 k / 4.2 k
-            const u32 n_sizes = (u32)__builtin_popcount(valid);
-            it.cost = stride == 1 ? 155u + 125u * n_sizes : (stride == 2 ? 105u + 90u * n_sizes : 140u + 40u * n_sizes);
+            it.cost = task_price(it.t);
             items.push_back(it);
             reach = std::max<u32>(reach, 24 + k0 + (half ? 11 : 15));
             covered_to = k0 + (half ? 4 : 8);
         }
     }
     if (items.size() > PRF_VMAX_TASKS) return false;
-    // longest-processing-time-first assignment to at most 4 waves
-    // (the derived k = 1 task is not dealt: it goes behind the k = 2 task, whose wave hands it the word, below)
+    // The deal.  The derived k = 1 task is not dealt: it goes behind the k = 2 task, whose wave hands it the word (below), and is
+    // priced with it.  Longest first onto the least loaded wave, then a local search over moves and swaps between any two waves
+    // (which is all a large plan gets), then -- up to EXHAUSTIVE_TASKS tasks -- every deal.
     std::vector<Item> sorted;
+    u32 handover = 0;
     for (const Item &it : items)
-        if (!(it.t.pad & PRF_TASK_DERIVED)) sorted.push_back(it);
-    const u32 nw = std::max<u32>(1, std::min<u32>(PRF_VMAX_WAVES, (u32)sorted.size()));
-    std::vector<std::vector<Item>> bins(nw);
-    std::vector<u32> load(nw, 0);
+        if (it.t.pad & PRF_TASK_DERIVED) handover = it.cost;
+        else sorted.push_back(it);
+    for (Item &it : sorted)
+        if (it.t.pad & PRF_TASK_RAISES_K1) it.cost += handover;
     std::stable_sort(sorted.begin(), sorted.end(), [](const Item &a, const Item &b) { return a.cost > b.cost; });
-    // The ticket for the workgroup's next launch slot is an atomic whose value the compiler waits for on the spot (~3 k
-    // cycles with a thousand workgroups drawing): it is dealt like a task, to the wave with the least other work -- or to
-    // a wave without tasks, if there is one.  (Tried and dropped: the waves of a workgroup pulling tasks from one list
-    // through an LDS counter at run time -- every wave's scan got 2-3 k cycles longer; the stride-1 group task cut in two
-    // halves of four sizes -- a half costs three quarters of the whole, its four blocks are LDS latency, not arithmetic.)
-    constexpr u32 TICKET_COST = 30;  // (round 3: the atomic's value is no longer waited for on the spot)
-    bool ticket_dealt = nw < (u32)PRF_VMAX_WAVES;
-    plan->ticket_wave = nw < (u32)PRF_VMAX_WAVES ? nw : 0;
-    for (const Item &it : sorted) {
-        if (!ticket_dealt && it.cost <= TICKET_COST) {
-            plan->ticket_wave = (u32)(std::min_element(load.begin(), load.end()) - load.begin());
-            load[plan->ticket_wave] += TICKET_COST;
-            ticket_dealt = true;
-        }
-        const u32 w = (u32)(std::min_element(load.begin(), load.end()) - load.begin());
-        bins[w].push_back(it);
-        load[w] += it.cost;
+    const size_t n_dealt = sorted.size();
+    std::vector<u32> cost(n_dealt), where(n_dealt, 0);
+    u32 load[PRF_VMAX_WAVES] = {};
+    for (size_t i = 0; i < n_dealt; i++) {
+        cost[i] = sorted[i].cost;
+        where[i] = (u32)(std::min_element(load, load + PRF_VMAX_WAVES) - load);
+        load[where[i]] += cost[i];
     }
-    if (!ticket_dealt) {
-        plan->ticket_wave = (u32)(std::min_element(load.begin(), load.end()) - load.begin());
-        load[plan->ticket_wave] += TICKET_COST;
-    }
-    // local improvement of the greedy deal: while the busiest wave can hand a task to, or swap a task with, another wave so that
-    // the larger of the two loads drops, do it (a dozen tasks: the default plan goes from 1980 to 1895 units of 10 cycles)
-    for (int round = 0; round < 64; round++) {
-        const u32 hi = (u32)(std::max_element(load.begin(), load.end()) - load.begin());
-        bool moved = false;
-        for (u32 o = 0; o < nw && !moved; o++) {
-            if (o == hi) continue;
-            for (size_t i = 0; i < bins[hi].size() && !moved; i++) {
-                const u32 ci = bins[hi][i].cost;
-                if (std::max(load[hi] - ci, load[o] + ci) < load[hi]) {  // move
-                    bins[o].push_back(bins[hi][i]);
-                    bins[hi].erase(bins[hi].begin() + (long)i);
-                    load[hi] -= ci;
-                    load[o] += ci;
-                    moved = true;
-                    break;
+    for (bool better = true; better;) {
+        better = false;
+        DealKey cur = deal_key(load);
+        for (size_t i = 0; i < n_dealt && !better; i++) {
+            for (u32 w = 0; w < (u32)PRF_VMAX_WAVES && !better; w++) {  // move task i to wave w
+                if (w == where[i]) continue;
+                u32 l2[PRF_VMAX_WAVES];
+                std::copy(load, load + PRF_VMAX_WAVES, l2);
+                l2[where[i]] -= cost[i];
+                l2[w] += cost[i];
+                if (deal_key(l2) < cur) {
+                    std::copy(l2, l2 + PRF_VMAX_WAVES, load);
+                    where[i] = w;
+                    better = true;
                 }
-                for (size_t j = 0; j < bins[o].size(); j++) {
-                    const u32 cj = bins[o][j].cost;
-                    if (cj < ci && std::max(load[hi] - ci + cj, load[o] + ci - cj) < load[hi]) {  // swap
-                        std::swap(bins[hi][i], bins[o][j]);
-                        load[hi] = load[hi] - ci + cj;
-                        load[o] = load[o] + ci - cj;
-                        moved = true;
-                        break;
-                    }
+            }
+            for (size_t j = i + 1; j < n_dealt && !better; j++) {  // swap the tasks i and j
+                if (where[i] == where[j] || cost[i] == cost[j]) continue;
+                u32 l2[PRF_VMAX_WAVES];
+                std::copy(load, load + PRF_VMAX_WAVES, l2);
+                l2[where[i]] = l2[where[i]] - cost[i] + cost[j];
+                l2[where[j]] = l2[where[j]] - cost[j] + cost[i];
+                if (deal_key(l2) < cur) {
+                    std::copy(l2, l2 + PRF_VMAX_WAVES, load);
+                    std::swap(where[i], where[j]);
+                    better = true;
                 }
             }
         }
-        if (!moved) break;
     }
+    constexpr size_t EXHAUSTIVE_TASKS = 16;
+    if (n_dealt <= EXHAUSTIVE_TASKS) {
+        DealSearch ds{cost, std::vector<u32>(n_dealt, 0), where};
+        ds.best = deal_key(load);
+        ds.go(0);
+        where = ds.best_where;
+    }
+    // waves in the order of their first (most expensive) task; the waves that got no task are the last ones
+    u32 n_used = 0;
+    {
+        u32 name[PRF_VMAX_WAVES];
+        std::fill(name, name + PRF_VMAX_WAVES, ~0u);
+        for (size_t i = 0; i < n_dealt; i++)
+            if (name[where[i]] == ~0u) name[where[i]] = n_used++;
+        for (size_t i = 0; i < n_dealt; i++) where[i] = name[where[i]];
+    }
+    const u32 nw = std::max<u32>(1, n_used);
+    std::vector<std::vector<Item>> bins(nw);
+    std::fill(load, load + PRF_VMAX_WAVES, 0u);
+    for (size_t i = 0; i < n_dealt; i++) {
+        Item it = sorted[i];
+        load[where[i]] += it.cost;
+        if (it.t.pad & PRF_TASK_RAISES_K1) it.cost -= handover;
+        bins[where[i]].push_back(it);
+    }
+    for (u32 w = 0; w < nw; w++) load[w] += FIRST_TASK;
+    // (the ticket for the workgroup's next launch slot is drawn by the wave that leaves the scan first, whichever that is; the plan
+    // names the wave it expects there.  Tried and dropped: the waves of a workgroup pulling tasks from one list through an LDS
+    // counter at run time -- every wave's scan got 2-3 k cycles longer; the stride-1 group task cut in two halves of four sizes -- a
+    // half costs three quarters of the whole, its four blocks are LDS latency, not arithmetic.)
+    plan->ticket_wave = (u32)(std::min_element(load, load + PRF_VMAX_WAVES) - load);
     // The order inside a wave: group tasks that examine every or every 2nd group first, exact tasks next, stride-4 group tasks
     // last.  The tile's record list takes 192 records, first come first served, and a record that finds no slot is verified on
     // the spot by the general routine with one look per examined group of its stream: four looks at stride 1, one at stride 4.
@@ -157,8 +258,8 @@ bool prf_vertical_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vp
     // records) the slots should therefore go to the small strides.  With the tasks in the order of the deal, the stride-1 task
     // of k = 8 .. 11 came behind two exact tasks, found the list full and verified alone for 103 k cycles, where the parent's
     // three waves with stride-4 tasks took 22 - 33 k each; first in its wave but behind two stride-4 tasks of other waves it
-    // still took 75 k (profiles/derived_k1_notes.md).  Only a plan that derives the k = 1 flags is dealt anew and ordered so:
-    // every other plan is what it was.
+    // still took 75 k (profiles/derived_k1_notes.md).  Only a plan that derives the k = 1 flags is ordered so; the others keep the
+    // order of falling cost.
     auto rank_of = [](const Item &it) { return it.t.kind != 0 ? 1 : (it.t.stride < 4 ? 0 : 2); };
     for (auto &bin : bins)
         if (derive_k1) std::stable_sort(bin.begin(), bin.end(), [&](const Item &a, const Item &b) {
@@ -176,18 +277,19 @@ bool prf_vertical_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vp
                         break;
                     }
     {
-        // default: the short, latency-bound phases (stage, the record waves of the verify phase, rows) at priority 2, the scan
-        // (long, plenty of independent arithmetic) and the flag waves (they wait at the barrier anyway) at 0.  Measured on
-        // the default workload (tools/prio_sweep.sh, gpurun_out/prio_sweep*.txt): 0.775 ms without priorities, 0.748-0.757
-        // with any setting that raises records and rows; random sequence (few candidates) is indifferent.
+        // The fields: prf_plan.h.  The short, latency-bound phases (stage, the record waves of the verify phase, rows) at
+        // priority 2, the scan (long, plenty of independent arithmetic) at 0; the hand-over between scan and verify, for which
+        // every wave of the workgroup waits, and the flag waves of the verify phase, whose flags are that phase's longest leg,
+        // have fields of their own.  The sweep: tools/prio_sweep.sh, profiles/scan_handover_notes.md section 4.
         // PRF_PRIO overrides in a diagnostic build (PRF_DIAG).
+        constexpr u32 PRIO_DEFAULT = 0x0A02u | (PRIO_HANDOVER << 12) | (PRIO_FLAGS << 6);
 #ifdef PRF_DIAG
-        static const u32 prio_cfg = getenv("PRF_PRIO") ? (u32)strtoul(getenv("PRF_PRIO"), nullptr, 0) : 0xA02u;
+        static const u32 prio_cfg = getenv("PRF_PRIO") ? (u32)strtoul(getenv("PRF_PRIO"), nullptr, 0) : PRIO_DEFAULT;
 #else
-        const u32 prio_cfg = 0xA02u;
+        const u32 prio_cfg = PRIO_DEFAULT;
 #endif
         plan->prio = prio_cfg;
-        const u32 busiest = *std::max_element(load.begin(), load.end());
+        const u32 busiest = *std::max_element(load, load + PRF_VMAX_WAVES);
         plan->slack_waves = 0;
         for (u32 w = 0; w < (u32)PRF_VMAX_WAVES; w++)
             if (w >= nw || 10u * load[w] < 9u * busiest) plan->slack_waves |= 1u << w;
@@ -233,6 +335,24 @@ bool prf_vertical_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vp
     return need_nc <= 80;
 }
 
+// A scan asks for its plan every time, and the deal looks at every deal of a small plan: the thread's last plan is kept.
+bool prf_vertical_plan(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, prf_vplan *plan) {
+    struct Last {
+        u32 key[4];
+        bool have, ok;
+        prf_vplan plan;
+    };
+    thread_local Last last = {};
+    if (!(last.have && last.key[0] == kmin && last.key[1] == kmax && last.key[2] == min_repeats && last.key[3] == min_span)) {
+        last.have = false;
+        last.plan = prf_vplan{};
+        last.ok = build_plan(kmin, kmax, min_repeats, min_span, &last.plan);
+        last.key[0] = kmin; last.key[1] = kmax; last.key[2] = min_repeats; last.key[3] = min_span;
+        last.have = true;
+    }
+    *plan = last.plan;
+    return last.ok;
+}
 
 int prf_plan_json(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, char *buf, u64 buf_len) {
     std::string out;
@@ -240,16 +360,19 @@ int prf_plan_json(u32 kmin, u32 kmax, u32 min_repeats, u32 min_span, char *buf, 
     if (!prf_vertical_plan(kmin, kmax, min_repeats, min_span, &plan)) {
         out = "{\"path\": \"generic\"}";
     } else {
-        char tmp[160];
-        snprintf(tmp, sizeof tmp, "{\"path\": \"fused\", \"waves\": %u, \"nc\": %u, \"lds_bytes\": %u, \"tasks\": [", plan.n_waves,
-                 plan.nc, plan.lds_bytes);
+        char tmp[240];
+        // (price: what the deal charges for the task, cycles per tile; window: the W' of its objective; first_task: what a wave with
+        // tasks is charged on top of their prices)
+        snprintf(tmp, sizeof tmp, "{\"path\": \"fused\", \"waves\": %u, \"nc\": %u, \"lds_bytes\": %u, \"window\": %u, \"first_task\": %u, \"tasks\": [",
+                 plan.n_waves, plan.nc, plan.lds_bytes, (unsigned)WINDOW_W, (unsigned)FIRST_TASK);
         out = tmp;
         bool first = true;
         for (u32 w = 0; w < plan.n_waves; w++)
             for (u32 ti = plan.wave_begin[w]; ti < plan.wave_begin[w + 1]; ti++) {
                 const prf_vtask &t = plan.tasks[ti];
-                snprintf(tmp, sizeof tmp, "%s{\"wave\": %u, \"kind\": %u, \"k0\": %u, \"valid\": %u, \"stride\": %u, \"derive\": %u}",
-                         first ? "" : ", ", w, (unsigned)t.kind, (unsigned)t.k0, (unsigned)t.valid, (unsigned)t.stride, (unsigned)(t.pad & 3u));
+                snprintf(tmp, sizeof tmp, "%s{\"wave\": %u, \"kind\": %u, \"k0\": %u, \"valid\": %u, \"stride\": %u, \"derive\": %u, \"price\": %u}",
+                         first ? "" : ", ", w, (unsigned)t.kind, (unsigned)t.k0, (unsigned)t.valid, (unsigned)t.stride, (unsigned)(t.pad & 3u),
+                         (unsigned)task_price(t));
                 out += tmp;
                 first = false;
             }

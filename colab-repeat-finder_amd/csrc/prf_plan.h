@@ -46,7 +46,8 @@ struct prf_vplan {
     u32 slack_waves;                            // bit w: wave w's scan work is < 90 % of the busiest wave's
     u32 per_cu;                                 // workgroups per CU the plan's LDS and the kernel's registers allow
     u32 prio;                                   // issue priorities (s_setprio), 2 bits each: stage | scan, busy wave << 2 | scan, slack
-                                                // wave << 4 | verify, flag waves << 6 | verify, record waves << 8 | rows << 10
+                                                // wave << 4 | verify, flag waves << 6 | verify, record waves << 8 | rows << 10 |
+                                                // hand-over (a wave's arrival from the scan to the barrier in front of verify) << 12
 };
 
 

@@ -301,9 +301,14 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
         if (vscan_skip(g) & 1u) allow = 0u;  // (diagnostic, PRF_SKIP: no flags, no records)
         run_tasks<NC>((prf_lds_cu4 *)vimg, hotw, nostart, g.plan, wave, lane, hasx, allow, em, task_dbg);  // (nostart: free on a clean tile)
     }
+    PRF_STAMP(17);  // the wave's arrival: the end of its last task
+    // From here to the second barrier -- arrival, window loads, window stores, pad loop, counters -- every wave of the workgroup waits
+    // for the last one: the shortest and most latency-bound stretch of the tile has a priority of its own (at the scan's it
+    // competed, at the lowest, with five other workgroups' scans).
+    set_prio((g.plan.prio >> 12) & 3u);
     // ---- 3a. R1 <- the window of the linear planes H and L (tile - 128 .. tile + 65536 + 1536 positions), in 16-byte units: unit
     // u < LW/2 is H's word pair u, the others L's; piece = 64 units = 1 KiB.  R1 is the image until the LAST wave has finished its
-    // tasks, so the window cannot be sent there earlier -- but the waves do not finish together (18.7 - 22.2 k cycles): the first
+    // tasks, so the window cannot be sent there earlier -- but the waves do not finish together (the plan's deal sees to that): the first
     // two to arrive load the window into registers (9 and 8 pieces: 36 / 32 VGPRs, free at this point) while they would
     // otherwise wait at the barrier, and store it behind the barrier.  The first version sent it by DMA behind the barrier: 2 - 4 k
     // cycles of HBM latency with every wave waiting.
@@ -315,10 +320,14 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
     {
         if (lane == 0) order = atomicAdd((u32 *)(cnt + CNT_ROWS0), 1u);  // (the counter is free until the barrier: arrival order)
         order = (u32)__builtin_amdgcn_readfirstlane((int)order);
+#ifdef PRF_STAMPS
+        if (g.dbg && lane == 0) g.dbg[((u64)slot * MAX_WAVES + wave) * PRF_STAMP_SLOTS + 18] = order;
+#endif
         const long long w0 = (long long)(tile * PRF_TILE_WORDS) - LIN_PRE;
         const u64 *wh = g.H + w0, *wl = g.L + w0;
-        const prf_u32x4 z = {0, 0, 0, 0};
-        static_for<0, 9>([&](auto ic) { wv[decltype(ic)::value] = z; });
+        // (the window registers are defined without an instruction: zeroed, every wave ran 36 v_mov_b32 here -- the two that load
+        // nothing as well -- in the stretch where all four are late; the stores behind the barrier sit under the loads' condition)
+        asm("" : "=v"(wv[0]), "=v"(wv[1]), "=v"(wv[2]), "=v"(wv[3]), "=v"(wv[4]), "=v"(wv[5]), "=v"(wv[6]), "=v"(wv[7]), "=v"(wv[8]));
         if (order < 2u) {
             const u32 first = order * 9u, n = order ? 8u : 9u;
             static_for<0, 9>([&](auto ic) {
@@ -339,8 +348,23 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
     u64 ticket = 0;
     const bool ticket_thread = order == 0u && lane == 0;
     if (ticket_thread) ticket = atomicAdd(ticket_word, 1ull);
-    PRF_STAMP(3);
+#ifdef PRF_STAMPS
+    {
+        // (stamps build only) slot 3: the arrival atomic is back and the window loads are issued; slot 20: the loads are in
+        // registers.  The loading waves wait for them HERE, where they would wait at the barrier anyway -- the product waits
+        // behind the barrier, in front of the stores -- so that the loads' latency is measured whether it is exposed or not;
+        // both clocks are read before either is stored (a stamp's store would be waited for with the loads).
+        const u64 t3 = __builtin_amdgcn_s_memtime();
+        if (order < 2u) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const u64 t20 = __builtin_amdgcn_s_memtime();
+        if (g.dbg && lane == 0) {
+            g.dbg[((u64)slot * MAX_WAVES + wave) * PRF_STAMP_SLOTS + 3] = t3;
+            g.dbg[((u64)slot * MAX_WAVES + wave) * PRF_STAMP_SLOTS + 20] = t20;
+        }
+    }
+#endif
     __syncthreads();  // the image is dead from here on
+    PRF_STAMP(19);
     {
         if (order < 2u) {
             const u32 first = order * 9u, n = order ? 8u : 9u;
@@ -352,6 +376,7 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
                 }
             });
         }
+        PRF_STAMP(21);
         // every sublist is padded to its capacity with the largest key of its quarter: no bounds test per key when the rows are
         // ranked (rows that the scan's overflow paths have listed already stay; the verification appends behind them)
         const prf_u32x4 n0 = *(prf_lds_cu4 *)(cnt + CNT_ROWS);
@@ -369,6 +394,7 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
             cnt[CNT_OVF0] = cnt[CNT_OVF];
             cnt[CNT_LONG0] = cnt[CNT_LONG];
         }
+        PRF_STAMP(22);
     }
     // The next launch slot's entry (a load from the launch list unless the list is one run of clean tiles): issued here by the
     // thread that drew the ticket, looked at behind the verification.
@@ -381,7 +407,8 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
     PRF_STAMP(4);
 
     // ---- 3b. verify, all waves together: every candidate -> a row in the tile's list, or nothing ----
-    // (the record waves are the critical path of this phase, the flag waves wait for them at the barrier below)
+    // (wave 0's flags are the longest leg of this phase since the echoes went, the record waves follow: both kinds have a priority
+    // field of their own)
     set_prio(wave < MAX_WAVES / 2 ? (g.plan.prio >> 6) & 3u : (g.plan.prio >> 8) & 3u);
     const u32 *xw = hasx ? reinterpret_cast<const u32 *>(g.X + ((long long)(tile * PRF_TILE_WORDS) - LIN_PRE)) : nullptr;
     typedef const unsigned short __attribute__((address_space(3))) prf_lds_cu16;
@@ -396,7 +423,7 @@ __global__ __launch_bounds__(NTH, 6) void prf_vscan_kernel(prf_vscan_args g) {
         n_recs = n_recs < (u32)REC_CAP ? n_recs : (u32)REC_CAP;
         n_flags = n_flags < (u32)FLAG_CAP ? n_flags : (u32)FLAG_CAP;
 #ifdef PRF_STAMPS
-        if (g.dbg && tid == 0) g.dbg[((u64)slot * MAX_WAVES + 0) * PRF_STAMP_SLOTS + 11] = (u64)n_flags | ((u64)n_recs << 32);  // (wave 0 has three tasks)
+        if (g.dbg && tid == 0) g.dbg[((u64)slot * MAX_WAVES + 0) * PRF_STAMP_SLOTS + 23] = (u64)n_flags | ((u64)n_recs << 32);
 #endif
         if (vscan_skip(g) & 2u) n_flags = 0;   // (diagnostic) the flags are listed but not verified
         if (vscan_skip(g) & 4u) n_recs = 0;    // (diagnostic) the same for the records

@@ -553,7 +553,7 @@ __device__ __forceinline__ void run_tasks(prf_lds_cu4 *vimg, prf_lds_u32 *hotw, 
         task.pad = (unsigned char)((tw1 >> 8) & 0xFFu);
         task.item0 = (unsigned short)(tw1 >> 16);
 #ifdef PRF_STAMPS
-        if (dbg && lane == 0 && ti - plan.wave_begin[wave] < 8u) dbg[8 + (ti - plan.wave_begin[wave])] = __builtin_amdgcn_s_memtime();
+        if (dbg && lane == 0 && ti - plan.wave_begin[wave] < 4u) dbg[8 + (ti - plan.wave_begin[wave])] = __builtin_amdgcn_s_memtime();
 #endif
         if (task.kind == 0) {
             const bool half = (task.valid & 0xF0u) == 0;

@@ -35,17 +35,47 @@ order = np.argsort(tot)[-6:]
 for i in order:
     print('slow WG', int(i), 'total', int(tot[i]), 'phases w0', [int(d[i, 0, j + 1] - d[i, 0, j]) for j in range(6)])
 
-# per-task durations (cycles, median over workgroups): slot 8+i = start of the wave's i-th task, slot 3 = end of scan
+# per-task durations (cycles, median over workgroups): slot 8+i = start of the wave's i-th task (the first four), slot 17 = end of
+# its last task, in front of the arrival atomic
 for w in range(4):
-    starts = [d[:, w, 8 + i] for i in range(8)]
+    starts = [d[:, w, 8 + i] for i in range(4)]
     out = []
-    for i in range(8):
+    for i in range(4):
         if np.median(starts[i]) == 0: break
-        nxt = starts[i + 1] if i + 1 < 8 and np.median(starts[i + 1]) != 0 else d[:, w, 3]
+        nxt = starts[i + 1] if i + 1 < 4 and np.median(starts[i + 1]) != 0 else d[:, w, 17]
         out.append(int(np.median(nxt - starts[i])))
-    print('wave', w, 'task cycles', out)
+    print('wave', w, 'task cycles', out, 'sum', sum(out), '; bar1 to first task', int(np.median(d[:, w, 8] - d[:, w, 2])),
+          '; last task to stamp 3', int(np.median(d[:, w, 3] - d[:, w, 17])), '; scan (stamp 2 to 17)', int(np.median(d[:, w, 17] - d[:, w, 2])))
 
-nf = d[:, 0, 11] & 0xFFFFFFFF; nr = d[:, 0, 11] >> 32
+# The hand-over from the scan to the verification.  Clock: cycles from the tile's stamp 0 (the earliest wave's).  Slot 17 = a
+# wave's arrival (end of its last task), 18 = its arrival order, 3 = arrival atomic back and window loads issued, 20 = the wave's
+# window loads are in registers (the stamps build waits for them in front of the first barrier), 19 = behind the first barrier,
+# 21 = its window stores are issued, 22 = pad loop and counters done (in front of the second barrier), 4 = behind the second
+# barrier (verify start).
+z = d[:, :, 0].min(axis=1)
+clk = lambda s: d[:, :, s] - z[:, None]
+print('arrival clock by wave:', [int(np.median(clk(17)[:, w])) for w in range(4)], ' verify start', int(np.median(clk(4).max(axis=1))))
+by_order = lambda s: np.stack([np.where(d[:, :, 18] == o, clk(s), 0).sum(axis=1) for o in range(4)], axis=1)
+valid = np.all(np.sort(d[:, :, 18], axis=1) == np.arange(4), axis=1)
+print('tiles whose four waves hold the orders 0..3:', int(valid.sum()), 'of', len(valid))
+for s, name in ((17, 'arrival (end of last task)'), (3, 'atomic back, loads issued'), (20, 'loads in registers'), (19, 'behind the first barrier'),
+                (21, 'window stores issued'), (22, 'pad loop and counters done'), (4, 'behind the second barrier')):
+    print('  %-28s by arrival order: %s' % (name, [int(np.median(by_order(s)[valid, o])) for o in range(4)]))
+o17, o3, o19, o20, o21, o22, o4 = (by_order(s)[valid] for s in (17, 3, 19, 20, 21, 22, 4))
+pct = lambda v: (int(np.median(v)), int(np.percentile(v, 10)), int(np.percentile(v, 90)))
+print('W (arrival of the 2nd wave to its loads being in registers): median %d p10 %d p90 %d; of that from the issue of the loads %d; 1st wave: W %d, from the issue %d' % (
+    *pct(o20[:, 1] - o17[:, 1]), int(np.median(o20[:, 1] - o3[:, 1])), int(np.median(o20[:, 0] - o17[:, 0])), int(np.median(o20[:, 0] - o3[:, 0]))))
+fixed = o3[:, 3] - o17[:, 3]
+print('fixed code behind the last arrival (its arrival to its stamp 3): median %d p10 %d p90 %d; to the barrier opening %d' % (*pct(fixed), int(np.median(o19.max(axis=1) - o17[:, 3]))))
+print("W' = W - that fixed code: median %d p10 %d p90 %d" % pct((o20[:, 1] - o17[:, 1]) - fixed))
+late = np.maximum(o20[:, 0], o20[:, 1]) - o3[:, 3]
+print('the later of the two loading waves has its data %d cycles (median; p10 %d p90 %d) after the last wave is ready for the barrier; share of tiles where that is later %.3f' % (*pct(late), float((late > 0).mean())))
+print('a4 - a2 (arrivals) median %d; a2 + W\' - a4 median %d' % (int(np.median(o17[:, 3] - o17[:, 1])), int(np.median(o20[:, 1] - fixed - o17[:, 3]))))
+print('between the barriers, by arrival order: stores %s, pad loop and counters %s, wait at the second barrier %s; barrier to barrier %d' % (
+    [int(np.median(o21[:, o] - o19[:, o])) for o in range(4)], [int(np.median(o22[:, o] - o21[:, o])) for o in range(4)],
+    [int(np.median(o4[:, o] - o22[:, o])) for o in range(4)], int(np.median(o4.max(axis=1) - o19.max(axis=1)))))
+
+nf = d[:, 0, 23] & 0xFFFFFFFF; nr = d[:, 0, 23] >> 32
 print('flags per tile: mean %.1f p10 %d p50 %d p90 %d p99 %d max %d; share <=64 %.3f <=128 %.3f <=192 %.3f <=256 %.3f' % (
     nf.mean(), *[int(np.percentile(nf, q)) for q in (10, 50, 90, 99, 100)], *[(nf <= c).mean() for c in (64, 128, 192, 256)]))
 print('records per tile: mean %.1f p10 %d p50 %d p90 %d p99 %d max %d; share <=64 %.3f <=128 %.3f <=192 %.3f' % (
