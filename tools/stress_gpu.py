@@ -44,6 +44,8 @@ while time.time() < t_end:
         kmax = min(kmax_all, kmin + rng.choice([0, 3, 10, 40, 140]))
         r = rng.choice([2, 2, 3, 3, 4, 6])
         span = rng.choice([1, 5, 9, 9, 12, 16, 30, 100])
+        if rng.random() < 0.5:                   # every span up to 40: the exact-task variants (K, M) the list above cannot reach
+            span = rng.randint(1, 40)
         rows, st = g.scan(kmin, kmax, r, span)
         got = [(int(x['contig']), int(x['start']), int(x['end']), int(x['k'])) for x in rows]
         want = []
