@@ -1,5 +1,5 @@
 // prf_host.h -- launch wrappers shared between the kernel translation units and the host ones that call them (context.cpp, genome.cpp, scan_host.cpp, literal_host.cpp, handoff.cpp,
-// interrupted.cpp, periodicity_host.cpp, dotplot_host.cpp, dotpair_host.cpp, dotruns_host.cpp).
+// interrupted.cpp, periodicity_host.cpp, dotplot_host.cpp, dotpair_host.cpp, dotruns_host.cpp, dotchain_host.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -214,3 +214,35 @@ struct prf_dotruns_args {
 hipError_t prf_launch_dotruns_find(hipStream_t s, prf_dotruns_args a);
 // one wave per entry of the long list; n_long = min(the list's count, long_cap), read by the caller
 hipError_t prf_launch_dotruns_long(hipStream_t s, const prf_dotruns_args &a, u64 n_long);
+
+// chains of those runs across short stretches of mismatches on one line (dotchain.hip).  The seeds are the rows the
+// two kernels above wrote at min_len = min_seed, left on the device; the ranges, the strand and the planes are read from the same
+// prf_dotruns_args, of which the chain kernels use pl, a_g_begin, na, b_g_begin, nb and strand only.
+struct prf_dotchain_dev {     // = prf_dotchain
+    u64 row, col, len, matches;
+    u32 dir, seeds;
+};
+struct prf_dotchain_long {    // a chain that is still going after PRF_DOTCHAIN_FOLLOW cells, with the state of its walk
+    u64 i0, j0;               // the line's first cell
+    u64 t0;                   // the first seed's first cell, in cells of the line
+    u64 end;                  // the last committed seed's last cell
+    u64 matches, pending;     // raw cells up to `end`; raw cells of the short runs behind it
+    u64 p;                    // the next cell to look at
+    u64 run_start;            // in_run: the first cell of the run that holds cell p - 1
+    u32 dir, seeds, in_run, reserved;
+};
+enum { PRF_DC_CHAINS = 0, PRF_DC_LONG = 1, PRF_DC_N = 2 };   // the chain kernels' two counters: chains found, entries of the long list
+struct prf_dotchain_args {
+    const prf_dotrun_dev *seed_rows;
+    u64 n_seeds;
+    u64 min_seed, min_len;
+    u32 max_gap;
+    prf_dotchain_dev *dst;    // `capacity` rows; chains behind them are counted, not written
+    u64 capacity;
+    prf_dotchain_long *longs;
+    u64 long_cap;
+    u64 *counters;            // PRF_DC_N words, zeroed by the caller
+};
+hipError_t prf_launch_dotchain_link(hipStream_t s, const prf_dotruns_args &a, const prf_dotchain_args &c);
+// one wave per entry of the long list; n_long = min(the list's count, long_cap), read by the caller
+hipError_t prf_launch_dotchain_long(hipStream_t s, const prf_dotruns_args &a, const prf_dotchain_args &c, u64 n_long);

@@ -14,6 +14,9 @@ draws the cells that only the minus strand keeps in a second colour:
 And --runs-tsv lists what the picture shows as coordinates: every maximal diagonal or anti-diagonal run of matching cells of at
 least --min-run cells, one line each.  With --runs-tsv and no -o no image is drawn, and no limit on the length applies:
     plot_dot_plot.py -R genome.fa chr22:20000000-21000000 --versus chr22:30000000-31000000 --strand both --runs-tsv runs.tsv --min-run 40
+--chains-tsv lists repeats with mismatches: exact runs of at least --min-seed cells on one diagonal or anti-diagonal, joined across
+at most --max-gap cells, with their matching cells, joined runs and identity:
+    plot_dot_plot.py -R genome.fa chr22:20000000-21000000 --versus chr22:30000000-31000000 --strand both --chains-tsv chains.tsv --min-seed 12 --max-gap 8 --min-chain 100 --min-identity 0.9
 """
 import argparse
 import gzip
@@ -209,9 +212,33 @@ def list_runs(ctx, seq, min_len, directions="both", versus=None, strand="+"):
     return out
 
 
+def chain_lines(name, begin, x_name, x_begin, strand, chains):
+    """The --chains-tsv lines of a list of chains (fields row, col, len, matches, dir, seeds): the columns of run_lines, then the
+    matching cells, the seeds and the identity matches / len to four decimals."""
+    lines = run_lines(name, begin, x_name, x_begin, strand, chains)
+    for line, matches, seeds, length in zip(lines, *(chains[f].tolist() for f in ("matches", "seeds", "len"))):
+        yield f"{line[:-1]}\t{matches}\t{seeds}\t{matches / length:.4f}\n"
+
+
+def list_chains(ctx, seq, min_seed, max_gap, min_len=0, min_identity=None, directions="both", versus=None, strand="+"):
+    """[(strand, chains)] of seq against versus, or against itself (then through prf_native.unique_chains), one entry per strand of
+    "+", "-" or "both"; min_identity filters here, on matches / len."""
+    import prf_native
+    out = []
+    for s in "+-":
+        if strand in (s, "both"):
+            chains = ctx.dotpair_chains(seq, seq if versus is None else versus, s, directions, min_seed, max_gap, min_len)
+            if versus is None:
+                chains = prf_native.unique_chains(chains, s)
+            if min_identity is not None:
+                chains = chains[prf_native.chain_identity(chains) >= min_identity]
+            out.append((s, chains))
+    return out
+
+
 def no_image(args):
-    """--runs-tsv without -o: the list is all that is asked for."""
-    return args.runs_tsv is not None and args.output_path is None
+    """--runs-tsv or --chains-tsv without -o: the list is all that is asked for."""
+    return (args.runs_tsv is not None or args.chains_tsv is not None) and args.output_path is None
 
 
 def build_parser():
@@ -245,7 +272,17 @@ def build_parser():
                         "Without -o no image is drawn, and sequences above 5,000 positions need no --block.")
     p.add_argument("--min-run", type=int, metavar="L", help="With --runs-tsv: the cells a run must have to be listed.")
     p.add_argument("--run-directions", choices=["main", "anti", "both"], default="both",
-                   help="With --runs-tsv: list diagonal runs, anti-diagonal runs or both (default).")
+                   help="With --runs-tsv or --chains-tsv: list diagonal runs, anti-diagonal runs or both (default).")
+    p.add_argument("--chains-tsv", metavar="PATH",
+                   help="Write the diagonal repeats with mismatches as a table: exact runs of at least --min-seed cells on one "
+                        "diagonal or anti-diagonal, joined wherever at most --max-gap cells lie between two of them. The columns of "
+                        "--runs-tsv (the length is the chain's span), then the matching cells, the joined runs and the identity "
+                        "(matches / span, four decimals). Needs --min-seed and --max-gap. Without --versus each repeat is listed "
+                        "once; without -o no image is drawn, and sequences above 5,000 positions need no --block.")
+    p.add_argument("--min-seed", type=int, metavar="S", help="With --chains-tsv: the cells an exact run must have to be joined or listed.")
+    p.add_argument("--max-gap", type=int, metavar="G", help="With --chains-tsv: the most cells between two joined runs, 0 to 4096.")
+    p.add_argument("--min-chain", type=int, metavar="L", help="With --chains-tsv: the cells a chain must span to be listed (default: no limit).")
+    p.add_argument("--min-identity", type=float, metavar="F", help="With --chains-tsv: list the chains with matches / span of at least this, 0 to 1.")
     p.add_argument("input_sequence_or_intervals_or_bed_files", nargs="+",
                    help="any mix of literal ACGT sequences, intervals chrom:start_0based-end, and BED files")
     return p
@@ -278,6 +315,20 @@ def resolve_inputs(args, parser):
         parser.error("--runs-tsv lists the runs of at least --min-run cells: give --min-run too")
     if args.min_run is not None and (args.runs_tsv is None or args.min_run < 1):
         parser.error(f"--min-run is set to {args.min_run}. It goes with --runs-tsv and must be at least 1.")
+    if args.chains_tsv is not None and (args.min_seed is None or args.max_gap is None):
+        parser.error("--chains-tsv joins runs of at least --min-seed cells across at most --max-gap cells: give --min-seed and --max-gap too")
+    for option, value in (("--min-seed", args.min_seed), ("--max-gap", args.max_gap), ("--min-chain", args.min_chain),
+                          ("--min-identity", args.min_identity)):
+        if value is not None and args.chains_tsv is None:
+            parser.error(f"{option} goes with --chains-tsv")
+    if args.min_seed is not None and args.min_seed < 1:
+        parser.error(f"--min-seed is set to {args.min_seed}. It must be at least 1.")
+    if args.max_gap is not None and not 0 <= args.max_gap <= 4096:
+        parser.error(f"--max-gap is set to {args.max_gap}. It must be between 0 and 4096.")
+    if args.min_chain is not None and args.min_chain < 0:
+        parser.error(f"--min-chain is set to {args.min_chain}. It must be at least 0.")
+    if args.min_identity is not None and not 0 <= args.min_identity <= 1:
+        parser.error(f"--min-identity is set to {args.min_identity}. It must be between 0 and 1.")
     inputs = args.input_sequence_or_intervals_or_bed_files
     out, n_intervals, cache = [], 0, {}
     for i, text in enumerate(inputs):
@@ -318,8 +369,8 @@ def resolve_inputs(args, parser):
                          f"Use --block B (a multiple of 64) to plot the density instead.")
         if not seq.isalpha() and seq:
             parser.error(f"Error: the sequence of {name} holds characters that are not letters")
-    if (args.tsv or args.runs_tsv) and len(out) > 1:
-        parser.error(f"{'--tsv' if args.tsv else '--runs-tsv'} takes one input sequence")
+    if (args.tsv or args.runs_tsv or args.chains_tsv) and len(out) > 1:
+        parser.error(f"{'--tsv' if args.tsv else '--runs-tsv' if args.runs_tsv else '--chains-tsv'} takes one input sequence")
     return out
 
 
@@ -374,8 +425,16 @@ def main(argv=None, context=None):
                 for strand, runs in listed:
                     f.writelines(run_lines(name, begin, x_name, x_begin, strand, runs))
             print(f"Wrote {args.runs_tsv} ({sum(len(runs) for _, runs in listed):,d} runs)")
-            if no_image(args):
-                continue
+        if args.chains_tsv:
+            x_name, x_begin = (name, begin) if versus is None else versus[:2]
+            listed = list_chains(_context(context), seq, args.min_seed, args.max_gap, args.min_chain or 0, args.min_identity,
+                                 args.run_directions, None if versus is None else columns, args.strand)
+            with open(args.chains_tsv, "wt") as f:
+                for strand, chains in listed:
+                    f.writelines(chain_lines(name, begin, x_name, x_begin, strand, chains))
+            print(f"Wrote {args.chains_tsv} ({sum(len(chains) for _, chains in listed):,d} chains)")
+        if no_image(args):
+            continue
         if args.block is None:
             matrix = dot_plot_matrix(seq, args.filter_threshold, 2 if args.show_filtered_pixels else 0, context=context,
                                      versus=None if versus is None else columns, strand=args.strand)

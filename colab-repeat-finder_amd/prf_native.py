@@ -131,6 +131,14 @@ DOTRUN_LONG_ROWS = 1 << 20           # PRF_DOTRUN_LONG_ROWS
 DOTRUN_PROBE = 16                    # PRF_DOTRUN_PROBE
 DOTRUN_FOLLOW = 2048                 # PRF_DOTRUN_FOLLOW
 DOTRUN_DEFAULT_CAPACITY = 1 << 16    # rows the first of the binding's two calls has room for
+# the entry points of the list of those runs chained across mismatches (include/prf_dotchain.h, which prf.h includes)
+DOTCHAIN_EXPORTS = ["prf_dotpair_chains", "prf_dotpair_chains_ex", "prf_dotpair_chains_seq"]
+DOTCHAIN_DTYPE = [("row", "<u8"), ("col", "<u8"), ("len", "<u8"), ("matches", "<u8"), ("dir", "<u4"), ("seeds", "<u4")]   # prf_dotchain, 40 bytes
+DOTCHAIN_MAX_GAP = 4096              # PRF_DOTCHAIN_MAX_GAP
+DOTCHAIN_MAX_ROWS = 1 << 24          # PRF_DOTCHAIN_MAX_ROWS
+DOTCHAIN_LONG_ROWS = 1 << 20         # PRF_DOTCHAIN_LONG_ROWS
+DOTCHAIN_FOLLOW = 2048               # PRF_DOTCHAIN_FOLLOW
+DOTCHAIN_DEFAULT_CAPACITY = 1 << 16  # rows the first of the binding's two calls has room for
 DIRECTIONS = {"main": 1, "anti": 2, "both": 3}
 DOT_LAUNCH_CELLS = 1 << 36   # PRF_DOT_LAUNCH_CELLS
 DOT_MAX_CELLS = 1 << 42      # PRF_DOT_MAX_CELLS
@@ -246,6 +254,10 @@ def load_library():
         lib.prf_dotpair_runs.argtypes = on_genome[:-6] + runs_tail
         lib.prf_dotpair_runs_ex.argtypes = on_genome[:-6] + runs_tail + [ctypes.c_uint64]
         lib.prf_dotpair_runs_seq.argtypes = one_shot[:-6] + runs_tail
+        chains_tail = runs_tail[:6] + [ctypes.c_uint64, ctypes.c_uint32] + runs_tail[6:]   # ... directions, min_seed, max_gap, min_len ...
+        lib.prf_dotpair_chains.argtypes = on_genome[:-6] + chains_tail
+        lib.prf_dotpair_chains_ex.argtypes = on_genome[:-6] + chains_tail + [ctypes.c_uint64]
+        lib.prf_dotpair_chains_seq.argtypes = one_shot[:-6] + chains_tail
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
         lib.prf_measure_hbm_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -477,6 +489,64 @@ def _runs(ctx, a_target, a_range, b_target, b_range, strand, directions, min_len
     return (runs, stats) if with_stats else runs
 
 
+def _chains(ctx, a_target, a_range, b_target, b_range, strand, directions, min_seed, max_gap, min_len, rows, cols, with_stats,
+            launch_cells):
+    """The one path of the dotpair_chains calls, as _runs: once with DOTCHAIN_DEFAULT_CAPACITY rows of room and once more with the
+    exact number if there were more."""
+    import numpy as np
+    if strand not in STRANDS:
+        raise ValueError(f"strand is {strand!r}. It must be '+' or '-'.")
+    if directions not in DIRECTIONS:
+        raise ValueError(f"directions is {directions!r}. It must be 'main', 'anti' or 'both'.")
+    if isinstance(min_seed, bool) or operator.index(min_seed) < 1:
+        raise ValueError(f"min_seed is set to {min_seed}. It must be at least 1.")
+    if isinstance(max_gap, bool) or not 0 <= operator.index(max_gap) <= DOTCHAIN_MAX_GAP:
+        raise ValueError(f"max_gap is set to {max_gap}. It must be 0 .. {DOTCHAIN_MAX_GAP}.")
+    if isinstance(min_len, bool) or operator.index(min_len) < 0:
+        raise ValueError(f"min_len is set to {min_len}. It must be at least 0.")
+    one_shot = not isinstance(a_target, tuple)
+    if one_shot == isinstance(b_target, tuple):
+        raise ValueError("the two ranges must both be sequences or both lie in a genome")
+    if not one_shot and b_target[0] is not a_target[0]:
+        raise ValueError("the two ranges must lie in the same resident genome")
+    a_where, na, a_end, _a_keep = _matrix_range(a_target, *a_range)
+    b_where, nb, b_end, _b_keep = _matrix_range(b_target, *b_range)
+    win, _ = _dot_window(na, nb, rows, cols, 0, None)
+    args = a_where + (a_range[0], a_end) + b_where + (b_range[0], b_end, STRANDS[strand]) + win + (DIRECTIONS[directions], min_seed,
+                                                                                               max_gap, min_len)
+    if one_shot:
+        fn, head, tail = ctx.lib.prf_dotpair_chains_seq, (ctx._h,), ()
+    else:
+        fn, head, tail = ctx.lib.prf_dotpair_chains_ex, (ctx._h, a_target[0]._h), (launch_cells,)
+    capacity = DOTCHAIN_DEFAULT_CAPACITY
+    while True:
+        out = np.zeros(max(1, capacity), dtype=DOTCHAIN_DTYPE)
+        n, stats = ctypes.c_uint64(0), ScanStats()
+        _check(ctx.lib, fn(*head, *args, out.ctypes.data_as(ctypes.c_void_p), capacity, ctypes.byref(n), ctypes.byref(stats), *tail))
+        if n.value <= capacity:
+            break
+        if n.value > DOTCHAIN_MAX_ROWS:
+            raise PrfError(PRF_EUNSUPPORTED, f"{n.value} chains are more than one call returns ({DOTCHAIN_MAX_ROWS}): ask for a larger "
+                                             "min_seed or min_len or for smaller windows")
+        capacity = n.value
+    chains = out[:n.value].copy()
+    return (chains, stats) if with_stats else chains
+
+
+def chain_identity(chains):
+    """matches / len of every chain of a list: the share of matching cells between the first seed's first and the last seed's
+    last cell (float64; 1.0 for a single exact run)."""
+    import numpy as np
+    return chains["matches"].astype(np.float64) / np.maximum(chains["len"], 1).astype(np.float64)
+
+
+def unique_chains(chains, strand="+"):
+    """The chains of a range compared with ITSELF, each repeat once, by unique_runs' rule on (row, col, len): raw is symmetric
+    there, so every chain has a mirror image across the main diagonal with the same len, matches and seeds.  Drops the trivial
+    diagonal on the plus strand."""
+    return unique_runs(chains, strand)
+
+
 def run_cells(runs, na, nb):
     """bool[na, nb]: the cells of a list of runs (fields row, col, len, dir; dir 1: (row + s, col + s), 2: (row + s, col - s))."""
     import numpy as np
@@ -557,6 +627,18 @@ class Genome:
         2 anti), sorted by (row, col, dir).  len is never clipped by the window: the lists of a partition into windows add up to
         the whole list.  run_cells() rasterises a list; unique_runs() halves the list of a range against itself."""
         return _runs(self.ctx, (self, a[0]), a[1:], (self, b[0]), b[1:], strand, directions, min_len, rows, cols, with_stats, launch_cells)
+
+    def dotpair_chains(self, a, b, strand="+", directions="both", min_seed=DOTRUN_PROBE, max_gap=0, min_len=0, rows=None, cols=None,
+                       with_stats=False, launch_cells=0):
+        """The diagonal repeats WITH MISMATCHES of the dot plot of dotpair_bits (prf_dotpair_chains): the runs of dotpair_runs at
+        min_len = min_seed (the seeds), joined along their diagonal or anti-diagonal wherever at most max_gap cells lie between
+        two of them.  A numpy structured array with the fields row, col (the first seed's start cell), len (up to the last seed's
+        last cell), matches (matching cells among those), dir and seeds, sorted by (row, col, dir); the chains whose start cell
+        lies in the window rows x cols and that have at least min_len cells.  Seeds and links are judged in the whole rectangle:
+        the lists of a partition into windows add up.  chain_identity() gives matches / len; unique_chains() halves the list of
+        a range against itself."""
+        return _chains(self.ctx, (self, a[0]), a[1:], (self, b[0]), b[1:], strand, directions, min_seed, max_gap, min_len, rows, cols,
+                       with_stats, launch_cells)
 
     @property
     def positions(self):
@@ -755,6 +837,11 @@ class Context:
                      cols=None, with_stats=False):
         """Genome.dotpair_runs for two sequences (str or bytes) in one call: load, list, free (prf_dotpair_runs_seq)."""
         return _runs(self, seq_a, a, seq_b, b, strand, directions, min_len, rows, cols, with_stats, 0)
+
+    def dotpair_chains(self, seq_a, seq_b, strand="+", directions="both", min_seed=DOTRUN_PROBE, max_gap=0, min_len=0, a=(0, None),
+                       b=(0, None), rows=None, cols=None, with_stats=False):
+        """Genome.dotpair_chains for two sequences (str or bytes) in one call: load, list, free (prf_dotpair_chains_seq)."""
+        return _chains(self, seq_a, a, seq_b, b, strand, directions, min_seed, max_gap, min_len, rows, cols, with_stats, 0)
 
     def period_counts(self, seq, kmin, kmax, window, begin=0, end=None, with_stats=False):
         """Genome.period_counts for one sequence (str or bytes) in one call: load, count, free (prf_period_counts_seq)."""

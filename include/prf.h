@@ -82,7 +82,7 @@ typedef struct prf_scan_stats {
     uint64_t n_candidates;  /* phase-1 candidates                                                        */
     uint64_t n_hits;        /* rows                                                                      */
     uint32_t n_launches;    /* kernel launches in the timed region                                       */
-    uint32_t path;          /* 0 = generic kernel, 1 = vertical bit-sliced kernel, 2 = literal lane, 3 = interrupted, 4 = periodicity, 5 = dot plot, 6 = dot plot of two ranges, 7 = its diagonal runs as a list */
+    uint32_t path;          /* 0 = generic kernel, 1 = vertical bit-sliced kernel, 2 = literal lane, 3 = interrupted, 4 = periodicity, 5 = dot plot, 6 = dot plot of two ranges, 7 = its diagonal runs as a list, 8 = those runs chained across mismatches */
     uint64_t seq;           /* fused path: serial number of this scan on its context (prf_scan_timings)  */
     uint32_t sorted_on_device; /* 1: the rows left the device sorted by (contig, start, end), no host sort   */
     uint32_t tiles_launched;   /* fused path: 65536-position tiles scanned (tiles of nothing but N are skipped)     */
@@ -341,6 +341,10 @@ int prf_measure_hbm_read(prf_ctx *ctx, uint64_t bytes, int iters, double *gbps);
 /* ---- the diagonal runs of that dot plot as coordinates: three more entry points, additions to ABI version 4,
  * declared in prf_dotruns.h, which this header includes here; prf_scan_stats.path = 7 is theirs. */
 #include "prf_dotruns.h"
+
+/* ---- those runs chained across short stretches of mismatches on one line: three more entry points, additions to
+ * ABI version 4, declared in prf_dotchain.h, which this header includes here; prf_scan_stats.path = 8 is theirs. */
+#include "prf_dotchain.h"
 
 #ifdef __cplusplus
 }

@@ -11,8 +11,11 @@ The runs cases (prf_dotpair_runs; the third field is min_len) count t
 2^16 x 2^16 window at min_len 11 and 32 on either strand, and -- runs-self -- all runs of 2^22 positions against themselves at
 min_len 64, four calls of 2^20 rows each (a call takes at most 2^42 cells), which sends the trivial diagonal through the long
 kernel.  They are counting calls (no destination): the time is the kernels', whatever the number of runs.
+The chains cases (prf_dotpair_chains; the third field is min_seed, the fifth max_gap) count the chains that start in the
+same 2^16 x 2^16 window at (11, 8) and (16, 64) on either strand, without a min_len, so that every head is a chain; the runs cases
+at min_len 11 and 16 are their yardstick.  They report the seeds and the event times of the seed kernels and of the chain kernels.
 
-    python3 tools/dotplot_timing.py [--length 50818468] [--runs 7] [--warmup 2] [--limit 300] [--only counts:16:3,bits:14:3:-,...]
+    python3 tools/dotplot_timing.py [--length 50818468] [--runs 7] [--warmup 2] [--limit 300] [--only counts:16:3,bits:14:3:-,chains:16:11:+:8,...]
 """
 import argparse
 import json
@@ -29,6 +32,7 @@ CASES = [("counts", 16, 3), ("counts", 16, 12), ("counts", 16, 64), ("counts", 2
 PAIR_CASES = [(mode, log2, t, strand) for strand in "+-" for mode, log2, t in CASES if (mode, log2, t) in
               (("counts", 16, 3), ("counts", 16, 12), ("bits", 14, 3), ("bits", 14, 12))]
 RUNS_CASES = [("runs", 16, 11, "+"), ("runs", 16, 11, "-"), ("runs", 16, 32, "+"), ("runs", 16, 32, "-"), ("runs-self", 22, 64, "+")]
+CHAINS_CASES = [case for strand in "+-" for case in (("runs", 16, 16, strand), ("chains", 16, 11, strand, 8), ("chains", 16, 16, strand, 64))]
 OFFSET = 30_000_000      # the window's first row and column: in the sequence, behind the stand-in's inner gap of N
 
 
@@ -67,17 +71,38 @@ def one_runs(args, genome, mode, side, min_len, strand):
                       "cells_per_s": round(side * side / med * 1e3, 0), "n_runs": runs}), flush=True)
 
 
+def one_chains(args, genome, side, min_seed, strand, max_gap):
+    """The chains cases: counting calls (both directions, no destination, no min_len) on the 2^16 window of the whole contig
+    against itself."""
+    import ctypes
+    import prf_native
+    whole, window, lib = (0, 0, (1 << 64) - 1), (OFFSET, OFFSET + side), genome.ctx.lib
+    ms, seeds_ms, chain_ms = [], [], []
+    for i in range(args.warmup + args.runs):
+        n, stats = ctypes.c_uint64(0), prf_native.ScanStats()
+        prf_native._check(lib, lib.prf_dotpair_chains(genome.ctx._h, genome._h, *whole, *whole, prf_native.STRANDS[strand], *window, *window, 3,
+                                                      min_seed, max_gap, 0, None, 0, ctypes.byref(n), ctypes.byref(stats)))
+        if i >= args.warmup:
+            ms.append(stats.scan_ms), seeds_ms.append(stats.phase1_ms), chain_ms.append(stats.phase2_ms)
+    med = statistics.median(ms)
+    print(json.dumps({"mode": "chains", "strand": strand, "rows": side, "cols": side, "min_seed": min_seed, "max_gap": max_gap, "runs": args.runs,
+                      "launches": stats.n_launches, "scan_ms_median": round(med, 4), "scan_ms_min": round(min(ms), 4), "scan_ms_max": round(max(ms), 4),
+                      "seed_kernels_ms_median": round(statistics.median(seeds_ms), 4), "chain_kernels_ms_median": round(statistics.median(chain_ms), 4),
+                      "chain_kernels_ms_max": round(max(chain_ms), 4), "cells_per_s": round(side * side / med * 1e3, 0),
+                      "n_seeds": stats.n_candidates, "n_heads": n.value, "n_chains": n.value}), flush=True)
+
+
 def one(args):
     import prf_native
     import synth  # noqa: F401
-    mode, log2, t, strand = (args.case.split(":") + [None])[:4]
+    mode, log2, t, strand, gap = (args.case.split(":") + [None, None])[:5]
     side, t = 1 << int(log2), int(t)
     if OFFSET + side > args.length:
         raise SystemExit(f"--length {args.length} is too short for a window of {side} positions from {OFFSET}")
     ctx = prf_native.Context(0)
     genome = ctx.standin([args.length], [args.seed], 64)
-    if mode.startswith("runs"):
-        one_runs(args, genome, mode, side, t, strand)
+    if mode.startswith("runs") or mode == "chains":
+        one_runs(args, genome, mode, side, t, strand) if mode != "chains" else one_chains(args, genome, side, t, strand, int(gap))
         genome.free()
         ctx.close()
         return
@@ -113,11 +138,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--limit", type=int, default=300, help="seconds per measurement (warm-up and timed calls together)")
     ap.add_argument("--only", help="comma-separated measurements to make, e.g. counts:16:3,bits:14:12 (default: all)")
-    ap.add_argument("--case", help="(internal) mode:log2 side:min_diagonal_run[:strand] -- run this one measurement in this process")
+    ap.add_argument("--case", help="(internal) mode:log2 side:min_diagonal_run[:strand[:max_gap]] -- run this one measurement in this process")
     args = ap.parse_args()
     if args.case:
         return one(args)
-    for case in [":".join(str(v) for v in c) for c in CASES + PAIR_CASES + RUNS_CASES]:
+    for case in [":".join(str(v) for v in c) for c in CASES + PAIR_CASES + RUNS_CASES + CHAINS_CASES]:
         mode, log2, t = case.split(":")[:3]
         if args.only and case not in args.only.split(","):
             continue
