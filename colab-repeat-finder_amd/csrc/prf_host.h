@@ -246,3 +246,26 @@ struct prf_dotchain_args {
 hipError_t prf_launch_dotchain_link(hipStream_t s, const prf_dotruns_args &a, const prf_dotchain_args &c);
 // one wave per entry of the long list; n_long = min(the list's count, long_cap), read by the caller
 hipError_t prf_launch_dotchain_long(hipStream_t s, const prf_dotruns_args &a, const prf_dotchain_args &c, u64 n_long);
+
+// junctions between those chains across neighbouring lines (dotlink.hip).  The seeds are the same rows, left on the
+// device; the heads kernel lists the seeds of the window that start a chain, the join kernel judges one head per wave.
+struct prf_dotlink_dev {      // = prf_dotlink
+    u64 row, col, from_row, from_col;
+    u32 dir;
+    int shift;
+    u32 gap, overlap;
+};
+enum { PRF_DL_HEADS = 0, PRF_DL_LINKS = 1, PRF_DL_N = 2 };   // the link kernels' two counters: chain heads of the window, links found
+struct prf_dotlink_args {
+    const prf_dotrun_dev *seed_rows;
+    u64 n_seeds;
+    u64 min_seed;
+    u32 max_gap, max_shift;
+    u32 *heads;               // n_seeds entries: the indices of the seeds that start a chain, in no order
+    prf_dotlink_dev *dst;     // `capacity` rows; links behind them are counted, not written
+    u64 capacity;
+    u64 *counters;            // PRF_DL_N words, zeroed by the caller
+};
+hipError_t prf_launch_dotlink_heads(hipStream_t s, const prf_dotruns_args &a, const prf_dotlink_args &c);
+// one wave per head; n_heads = the heads' count, read by the caller
+hipError_t prf_launch_dotlink_join(hipStream_t s, const prf_dotruns_args &a, const prf_dotlink_args &c, u64 n_heads);

@@ -17,6 +17,8 @@ least --min-run cells, one line each.  With --runs-tsv and no -o no image is dra
 --chains-tsv lists repeats with mismatches: exact runs of at least --min-seed cells on one diagonal or anti-diagonal, joined across
 at most --max-gap cells, with their matching cells, joined runs and identity:
     plot_dot_plot.py -R genome.fa chr22:20000000-21000000 --versus chr22:30000000-31000000 --strand both --chains-tsv chains.tsv --min-seed 12 --max-gap 8 --min-chain 100 --min-identity 0.9
+--groups-tsv lists repeats with mismatches AND indels: those chains, joined across junctions of at most --max-shift diagonals:
+    plot_dot_plot.py -R genome.fa chr22:20000000-21000000 --versus chr22:30000000-31000000 --strand both --groups-tsv groups.tsv --min-seed 12 --max-gap 8 --max-shift 4 --min-group 200 --min-identity 0.85
 """
 import argparse
 import gzip
@@ -236,9 +238,44 @@ def list_chains(ctx, seq, min_seed, max_gap, min_len=0, min_identity=None, direc
     return out
 
 
+def group_lines(name, begin, x_name, x_begin, strand, groups):
+    """The --groups-tsv lines of a list of groups (prf_native.join_chains): name, a_start, a_end, X's name, b_start, b_end (ends
+    exclusive, forward coordinates on both strands), strand, direction, the rows and the columns spanned, the matching cells, the
+    chains, the seeds, the inserted or deleted bases (the sum of |shift|), the cells of the junctions' gaps, 1 if the group begins
+    outside the rectangle's window (0 otherwise) and the identity matches / max(span_a, span_b) to four decimals."""
+    import prf_native
+    fields = ("row", "col", "end_row", "end_col", "dir", "span_a", "span_b", "matches", "chains", "seeds", "indel", "gap_cells", "open")
+    identity = prf_native.group_identity(groups).tolist()
+    for (row, col, end_row, end_col, direction, span_a, span_b, matches, chains, seeds, indel, gap_cells, is_open), share in zip(
+            zip(*(groups[f].tolist() for f in fields)), identity):
+        yield (f"{name}\t{begin + row}\t{begin + end_row + 1}\t{x_name}\t{x_begin + min(col, end_col)}\t{x_begin + max(col, end_col) + 1}\t"
+               f"{strand}\t{'main' if direction == 1 else 'anti'}\t{span_a}\t{span_b}\t{matches}\t{chains}\t{seeds}\t{indel}\t{gap_cells}\t"
+               f"{int(is_open)}\t{share:.4f}\n")
+
+
+def list_groups(ctx, seq, min_seed, max_gap, max_shift, min_group=0, min_identity=None, directions="both", versus=None, strand="+"):
+    """[(strand, groups)] of seq against versus, or against itself (then BOTH mirror images are listed: the tie-break on the sign
+    of the shift is not mirror-symmetric), one entry per strand of "+", "-" or "both": the chains at min_len = 0 and the links of
+    the whole rectangle, folded by prf_native.join_chains; min_group (on the longer span) and min_identity filter here."""
+    import prf_native
+    out = []
+    columns = seq if versus is None else versus
+    for s in "+-":
+        if strand in (s, "both"):
+            chains = ctx.dotpair_chains(seq, columns, s, directions, min_seed, max_gap, 0)
+            links = ctx.dotpair_links(seq, columns, s, directions, min_seed, max_gap, max_shift)
+            groups = prf_native.join_chains(chains, links, len(columns))
+            if min_group:
+                groups = groups[np.maximum(groups["span_a"], groups["span_b"]) >= min_group]
+            if min_identity is not None:
+                groups = groups[prf_native.group_identity(groups) >= min_identity]
+            out.append((s, groups))
+    return out
+
+
 def no_image(args):
-    """--runs-tsv or --chains-tsv without -o: the list is all that is asked for."""
-    return (args.runs_tsv is not None or args.chains_tsv is not None) and args.output_path is None
+    """--runs-tsv, --chains-tsv or --groups-tsv without -o: the list is all that is asked for."""
+    return (args.runs_tsv is not None or args.chains_tsv is not None or args.groups_tsv is not None) and args.output_path is None
 
 
 def build_parser():
@@ -272,17 +309,32 @@ def build_parser():
                         "Without -o no image is drawn, and sequences above 5,000 positions need no --block.")
     p.add_argument("--min-run", type=int, metavar="L", help="With --runs-tsv: the cells a run must have to be listed.")
     p.add_argument("--run-directions", choices=["main", "anti", "both"], default="both",
-                   help="With --runs-tsv or --chains-tsv: list diagonal runs, anti-diagonal runs or both (default).")
+                   help="With --runs-tsv, --chains-tsv or --groups-tsv: list diagonal runs, anti-diagonal runs or both (default).")
     p.add_argument("--chains-tsv", metavar="PATH",
                    help="Write the diagonal repeats with mismatches as a table: exact runs of at least --min-seed cells on one "
                         "diagonal or anti-diagonal, joined wherever at most --max-gap cells lie between two of them. The columns of "
                         "--runs-tsv (the length is the chain's span), then the matching cells, the joined runs and the identity "
                         "(matches / span, four decimals). Needs --min-seed and --max-gap. Without --versus each repeat is listed "
                         "once; without -o no image is drawn, and sequences above 5,000 positions need no --block.")
-    p.add_argument("--min-seed", type=int, metavar="S", help="With --chains-tsv: the cells an exact run must have to be joined or listed.")
-    p.add_argument("--max-gap", type=int, metavar="G", help="With --chains-tsv: the most cells between two joined runs, 0 to 4096.")
+    p.add_argument("--min-seed", type=int, metavar="S",
+                   help="With --chains-tsv or --groups-tsv: the cells an exact run must have to be joined or listed.")
+    p.add_argument("--max-gap", type=int, metavar="G",
+                   help="With --chains-tsv or --groups-tsv: the most cells between two joined runs, 0 to 4096.")
     p.add_argument("--min-chain", type=int, metavar="L", help="With --chains-tsv: the cells a chain must span to be listed (default: no limit).")
-    p.add_argument("--min-identity", type=float, metavar="F", help="With --chains-tsv: list the chains with matches / span of at least this, 0 to 1.")
+    p.add_argument("--min-identity", type=float, metavar="F",
+                   help="With --chains-tsv or --groups-tsv: list the chains (groups) with matches / span of at least this, 0 to 1.")
+    p.add_argument("--groups-tsv", metavar="PATH",
+                   help="Write the repeats with mismatches and indels as a table: the chains of --chains-tsv at --min-seed and "
+                        "--max-gap, joined across junctions to a chain that starts 1 to --max-shift diagonals away, on the whole "
+                        "rectangle of the two ranges. One line per group: name, a_start, a_end, X's name, b_start, b_end, strand, "
+                        "direction, rows spanned, columns spanned, matching cells, chains, seeds, inserted or deleted bases, cells "
+                        "of the junctions' gaps, 0 (1: the group begins outside the rectangle) and the identity matches / longer "
+                        "span. Needs --min-seed, --max-gap and --max-shift. Without --versus BOTH mirror images of a repeat are "
+                        "written (the tie-break between an insertion and a deletion is not mirror-symmetric) and the trivial "
+                        "diagonal too; without -o no image is drawn, and sequences above 5,000 positions need no --block.")
+    p.add_argument("--max-shift", type=int, metavar="D", help="With --groups-tsv: the most diagonals between two joined chains, 1 to 32.")
+    p.add_argument("--min-group", type=int, metavar="L",
+                   help="With --groups-tsv: the rows or columns a group must span to be listed (default: no limit).")
     p.add_argument("input_sequence_or_intervals_or_bed_files", nargs="+",
                    help="any mix of literal ACGT sequences, intervals chrom:start_0based-end, and BED files")
     return p
@@ -317,10 +369,21 @@ def resolve_inputs(args, parser):
         parser.error(f"--min-run is set to {args.min_run}. It goes with --runs-tsv and must be at least 1.")
     if args.chains_tsv is not None and (args.min_seed is None or args.max_gap is None):
         parser.error("--chains-tsv joins runs of at least --min-seed cells across at most --max-gap cells: give --min-seed and --max-gap too")
-    for option, value in (("--min-seed", args.min_seed), ("--max-gap", args.max_gap), ("--min-chain", args.min_chain),
-                          ("--min-identity", args.min_identity)):
-        if value is not None and args.chains_tsv is None:
-            parser.error(f"{option} goes with --chains-tsv")
+    if args.groups_tsv is not None and (args.min_seed is None or args.max_gap is None or args.max_shift is None):
+        parser.error("--groups-tsv joins the chains of --min-seed and --max-gap across at most --max-shift diagonals: give --min-seed, "
+                     "--max-gap and --max-shift too")
+    for option, value in (("--min-seed", args.min_seed), ("--max-gap", args.max_gap), ("--min-identity", args.min_identity)):
+        if value is not None and args.chains_tsv is None and args.groups_tsv is None:
+            parser.error(f"{option} goes with --chains-tsv or --groups-tsv")
+    if args.min_chain is not None and args.chains_tsv is None:
+        parser.error("--min-chain goes with --chains-tsv")
+    for option, value in (("--max-shift", args.max_shift), ("--min-group", args.min_group)):
+        if value is not None and args.groups_tsv is None:
+            parser.error(f"{option} goes with --groups-tsv")
+    if args.max_shift is not None and not 1 <= args.max_shift <= 32:
+        parser.error(f"--max-shift is set to {args.max_shift}. It must be between 1 and 32.")
+    if args.min_group is not None and args.min_group < 0:
+        parser.error(f"--min-group is set to {args.min_group}. It must be at least 0.")
     if args.min_seed is not None and args.min_seed < 1:
         parser.error(f"--min-seed is set to {args.min_seed}. It must be at least 1.")
     if args.max_gap is not None and not 0 <= args.max_gap <= 4096:
@@ -369,8 +432,9 @@ def resolve_inputs(args, parser):
                          f"Use --block B (a multiple of 64) to plot the density instead.")
         if not seq.isalpha() and seq:
             parser.error(f"Error: the sequence of {name} holds characters that are not letters")
-    if (args.tsv or args.runs_tsv or args.chains_tsv) and len(out) > 1:
-        parser.error(f"{'--tsv' if args.tsv else '--runs-tsv' if args.runs_tsv else '--chains-tsv'} takes one input sequence")
+    if (args.tsv or args.runs_tsv or args.chains_tsv or args.groups_tsv) and len(out) > 1:
+        parser.error(f"{'--tsv' if args.tsv else '--runs-tsv' if args.runs_tsv else '--chains-tsv' if args.chains_tsv else '--groups-tsv'} "
+                     "takes one input sequence")
     return out
 
 
@@ -433,6 +497,14 @@ def main(argv=None, context=None):
                 for strand, chains in listed:
                     f.writelines(chain_lines(name, begin, x_name, x_begin, strand, chains))
             print(f"Wrote {args.chains_tsv} ({sum(len(chains) for _, chains in listed):,d} chains)")
+        if args.groups_tsv:
+            x_name, x_begin = (name, begin) if versus is None else versus[:2]
+            listed = list_groups(_context(context), seq, args.min_seed, args.max_gap, args.max_shift, args.min_group or 0, args.min_identity,
+                                 args.run_directions, None if versus is None else columns, args.strand)
+            with open(args.groups_tsv, "wt") as f:
+                for strand, groups in listed:
+                    f.writelines(group_lines(name, begin, x_name, x_begin, strand, groups))
+            print(f"Wrote {args.groups_tsv} ({sum(len(groups) for _, groups in listed):,d} groups)")
         if no_image(args):
             continue
         if args.block is None:

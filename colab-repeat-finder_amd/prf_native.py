@@ -139,6 +139,17 @@ DOTCHAIN_MAX_ROWS = 1 << 24          # PRF_DOTCHAIN_MAX_ROWS
 DOTCHAIN_LONG_ROWS = 1 << 20         # PRF_DOTCHAIN_LONG_ROWS
 DOTCHAIN_FOLLOW = 2048               # PRF_DOTCHAIN_FOLLOW
 DOTCHAIN_DEFAULT_CAPACITY = 1 << 16  # rows the first of the binding's two calls has room for
+# the entry points of the list of junctions between those chains (include/prf_dotlink.h, which prf.h includes)
+DOTLINK_EXPORTS = ["prf_dotpair_links", "prf_dotpair_links_ex", "prf_dotpair_links_seq"]
+DOTLINK_DTYPE = [("row", "<u8"), ("col", "<u8"), ("from_row", "<u8"), ("from_col", "<u8"), ("dir", "<u4"), ("shift", "<i4"),
+                 ("gap", "<u4"), ("overlap", "<u4")]   # prf_dotlink, 48 bytes
+DOTLINK_MAX_SHIFT = 32               # PRF_DOTLINK_MAX_SHIFT
+DOTLINK_OVERLAP = 16                 # PRF_DOTLINK_OVERLAP
+DOTLINK_DEFAULT_CAPACITY = 1 << 16   # rows the first of the binding's two calls has room for
+# one row of join_chains per group of chains joined by links
+DOTGROUP_DTYPE = [("row", "<u8"), ("col", "<u8"), ("end_row", "<u8"), ("end_col", "<u8"), ("span_a", "<u8"), ("span_b", "<u8"),
+                  ("matches", "<u8"), ("gap_cells", "<u8"), ("dir", "<u4"), ("chains", "<u4"), ("seeds", "<u4"), ("indel", "<u4"),
+                  ("open", "?")]
 DIRECTIONS = {"main": 1, "anti": 2, "both": 3}
 DOT_LAUNCH_CELLS = 1 << 36   # PRF_DOT_LAUNCH_CELLS
 DOT_MAX_CELLS = 1 << 42      # PRF_DOT_MAX_CELLS
@@ -258,6 +269,10 @@ def load_library():
         lib.prf_dotpair_chains.argtypes = on_genome[:-6] + chains_tail
         lib.prf_dotpair_chains_ex.argtypes = on_genome[:-6] + chains_tail + [ctypes.c_uint64]
         lib.prf_dotpair_chains_seq.argtypes = one_shot[:-6] + chains_tail
+        links_tail = runs_tail[:6] + [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32] + runs_tail[7:]   # ... min_seed, max_gap, max_shift ...
+        lib.prf_dotpair_links.argtypes = on_genome[:-6] + links_tail
+        lib.prf_dotpair_links_ex.argtypes = on_genome[:-6] + links_tail + [ctypes.c_uint64]
+        lib.prf_dotpair_links_seq.argtypes = one_shot[:-6] + links_tail
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
         lib.prf_measure_hbm_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -533,6 +548,107 @@ def _chains(ctx, a_target, a_range, b_target, b_range, strand, directions, min_s
     return (chains, stats) if with_stats else chains
 
 
+def _links(ctx, a_target, a_range, b_target, b_range, strand, directions, min_seed, max_gap, max_shift, rows, cols, with_stats,
+           launch_cells):
+    """The one path of the dotpair_links calls, as _chains: once with DOTLINK_DEFAULT_CAPACITY rows of room and once more with the
+    exact number if there were more."""
+    import numpy as np
+    if strand not in STRANDS:
+        raise ValueError(f"strand is {strand!r}. It must be '+' or '-'.")
+    if directions not in DIRECTIONS:
+        raise ValueError(f"directions is {directions!r}. It must be 'main', 'anti' or 'both'.")
+    if isinstance(min_seed, bool) or operator.index(min_seed) < 1:
+        raise ValueError(f"min_seed is set to {min_seed}. It must be at least 1.")
+    if isinstance(max_gap, bool) or not 0 <= operator.index(max_gap) <= DOTCHAIN_MAX_GAP:
+        raise ValueError(f"max_gap is set to {max_gap}. It must be 0 .. {DOTCHAIN_MAX_GAP}.")
+    if isinstance(max_shift, bool) or not 1 <= operator.index(max_shift) <= DOTLINK_MAX_SHIFT:
+        raise ValueError(f"max_shift is set to {max_shift}. It must be 1 .. {DOTLINK_MAX_SHIFT}.")
+    one_shot = not isinstance(a_target, tuple)
+    if one_shot == isinstance(b_target, tuple):
+        raise ValueError("the two ranges must both be sequences or both lie in a genome")
+    if not one_shot and b_target[0] is not a_target[0]:
+        raise ValueError("the two ranges must lie in the same resident genome")
+    a_where, na, a_end, _a_keep = _matrix_range(a_target, *a_range)
+    b_where, nb, b_end, _b_keep = _matrix_range(b_target, *b_range)
+    win, _ = _dot_window(na, nb, rows, cols, 0, None)
+    args = a_where + (a_range[0], a_end) + b_where + (b_range[0], b_end, STRANDS[strand]) + win + (DIRECTIONS[directions], min_seed,
+                                                                                               max_gap, max_shift)
+    if one_shot:
+        fn, head, tail = ctx.lib.prf_dotpair_links_seq, (ctx._h,), ()
+    else:
+        fn, head, tail = ctx.lib.prf_dotpair_links_ex, (ctx._h, a_target[0]._h), (launch_cells,)
+    capacity = DOTLINK_DEFAULT_CAPACITY
+    while True:
+        out = np.zeros(max(1, capacity), dtype=DOTLINK_DTYPE)
+        n, stats = ctypes.c_uint64(0), ScanStats()
+        _check(ctx.lib, fn(*head, *args, out.ctypes.data_as(ctypes.c_void_p), capacity, ctypes.byref(n), ctypes.byref(stats), *tail))
+        if n.value <= capacity:
+            break
+        if n.value > DOTCHAIN_MAX_ROWS:
+            raise PrfError(PRF_EUNSUPPORTED, f"{n.value} links are more than one call returns ({DOTCHAIN_MAX_ROWS}): ask for a larger "
+                                             "min_seed or for smaller windows")
+        capacity = n.value
+    links = out[:n.value].copy()
+    return (links, stats) if with_stats else links
+
+
+def join_chains(chains, links, nb=None):
+    """The gapped repeats of a window: the chains of dotpair_chains (fetched at min_len = 0) joined along the links of
+    dotpair_links of the same window, min_seed and max_gap.  Every chain has at most one link in and one out, so the links form
+    paths; one row of DOTGROUP_DTYPE per path (a chain without links is a path of one), in the order of the paths' first chains:
+    row, col, dir of the first chain; end_row, end_col: the last chain's last cell; span_a, span_b: the rows and the columns from
+    the first to the last cell; matches: the chains' matches minus the overlaps of the links inside the group (the cells of a
+    successor's first seed that lie in front of its predecessor's end count once); chains, seeds; indel: the sum of |shift|;
+    gap_cells: the sum of the links' gaps; open: a link into the group's first chain names a predecessor that is not in
+    `chains`, so the group begins outside the window.  nb (the columns of the rectangle) is not needed: both lists hold columns."""
+    import numpy as np
+    n = len(chains)
+    length = chains["len"].astype(np.int64)
+    first = {key: k for k, key in enumerate(zip(chains["row"].tolist(), chains["col"].tolist(), chains["dir"].tolist()))}
+    last_col = chains["col"].astype(np.int64) + np.where(chains["dir"] == 2, -(length - 1), length - 1)
+    last_row = chains["row"].astype(np.int64) + length - 1
+    last = {key: k for k, key in enumerate(zip(last_row.tolist(), last_col.tolist(), chains["dir"].tolist()))}
+    nxt, link_of, has_in, is_open = [-1] * n, [-1] * n, [False] * n, [False] * n
+    for k, (row, col, from_row, from_col, d) in enumerate(zip(*(links[f].tolist() for f in ("row", "col", "from_row", "from_col", "dir")))):
+        y = first.get((row, col, d))
+        if y is None:
+            raise ValueError(f"the link into ({row}, {col}, dir {d}) names a successor that is not in the list of chains: "
+                             "join_chains needs the chains of the same window, min_seed and max_gap, fetched at min_len = 0")
+        x = last.get((from_row, from_col, d))
+        if x is None:
+            is_open[y] = True
+        else:
+            nxt[x], link_of[x], has_in[y] = y, k, True
+    out = np.zeros(n - sum(has_in), dtype=DOTGROUP_DTYPE)
+    matches, seeds = chains["matches"].tolist(), chains["seeds"].tolist()
+    shift, gap, overlap = (links[f].tolist() for f in ("shift", "gap", "overlap"))
+    at = 0
+    for k in range(n):
+        if has_in[k]:
+            continue
+        g = out[at]
+        g["row"], g["col"], g["dir"], g["open"] = chains["row"][k], chains["col"][k], chains["dir"][k], is_open[k]
+        total = n_seeds = n_chains = indel = gap_cells = 0
+        while True:
+            total, n_seeds, n_chains = total + matches[k], n_seeds + seeds[k], n_chains + 1
+            if nxt[k] < 0:
+                break
+            via = link_of[k]
+            total, indel, gap_cells = total - overlap[via], indel + abs(shift[via]), gap_cells + gap[via]
+            k = nxt[k]
+        g["end_row"], g["end_col"] = last_row[k], last_col[k]
+        g["span_a"], g["span_b"] = last_row[k] - int(g["row"]) + 1, abs(int(last_col[k]) - int(g["col"])) + 1
+        g["matches"], g["seeds"], g["chains"], g["indel"], g["gap_cells"] = total, n_seeds, n_chains, indel, gap_cells
+        at += 1
+    return out
+
+
+def group_identity(groups):
+    """matches / max(span_a, span_b) of every group of join_chains (float64)."""
+    import numpy as np
+    return groups["matches"].astype(np.float64) / np.maximum(np.maximum(groups["span_a"], groups["span_b"]), 1).astype(np.float64)
+
+
 def chain_identity(chains):
     """matches / len of every chain of a list: the share of matching cells between the first seed's first and the last seed's
     last cell (float64; 1.0 for a single exact run)."""
@@ -639,6 +755,18 @@ class Genome:
         a range against itself."""
         return _chains(self.ctx, (self, a[0]), a[1:], (self, b[0]), b[1:], strand, directions, min_seed, max_gap, min_len, rows, cols,
                        with_stats, launch_cells)
+
+    def dotpair_links(self, a, b, strand="+", directions="both", min_seed=DOTRUN_PROBE, max_gap=0, max_shift=1, rows=None, cols=None,
+                      with_stats=False, launch_cells=0):
+        """The INDEL JUNCTIONS between the chains of dotpair_chains at the same min_seed and max_gap (prf_dotpair_links): chain
+        X ends, chain Y starts 1 .. max_shift lines away, at most max_gap cells behind (or up to min(min_seed - 1, 16) cells in
+        front), and each is the other's best such neighbour.  A numpy structured array with the fields row, col (Y's first cell:
+        the key of Y's row in the list of chains), from_row, from_col (X's last cell), dir, shift (positive: bases only B has),
+        gap and overlap, sorted by (row, col, dir); the links whose (row, col) lies in the window rows x cols.  Links are judged
+        in the whole rectangle: the lists of a partition into windows add up.  join_chains() folds the two lists into gapped
+        repeats."""
+        return _links(self.ctx, (self, a[0]), a[1:], (self, b[0]), b[1:], strand, directions, min_seed, max_gap, max_shift, rows, cols,
+                      with_stats, launch_cells)
 
     @property
     def positions(self):
@@ -842,6 +970,11 @@ class Context:
                        b=(0, None), rows=None, cols=None, with_stats=False):
         """Genome.dotpair_chains for two sequences (str or bytes) in one call: load, list, free (prf_dotpair_chains_seq)."""
         return _chains(self, seq_a, a, seq_b, b, strand, directions, min_seed, max_gap, min_len, rows, cols, with_stats, 0)
+
+    def dotpair_links(self, seq_a, seq_b, strand="+", directions="both", min_seed=DOTRUN_PROBE, max_gap=0, max_shift=1, a=(0, None),
+                      b=(0, None), rows=None, cols=None, with_stats=False):
+        """Genome.dotpair_links for two sequences (str or bytes) in one call: load, list, free (prf_dotpair_links_seq)."""
+        return _links(self, seq_a, a, seq_b, b, strand, directions, min_seed, max_gap, max_shift, rows, cols, with_stats, 0)
 
     def period_counts(self, seq, kmin, kmax, window, begin=0, end=None, with_stats=False):
         """Genome.period_counts for one sequence (str or bytes) in one call: load, count, free (prf_period_counts_seq)."""

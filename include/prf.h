@@ -346,6 +346,10 @@ int prf_measure_hbm_read(prf_ctx *ctx, uint64_t bytes, int iters, double *gbps);
  * ABI version 4, declared in prf_dotchain.h, which this header includes here; prf_scan_stats.path = 8 is theirs. */
 #include "prf_dotchain.h"
 
+/* ---- the junctions between those chains across neighbouring lines (indels): three more entry points, additions to
+ * ABI version 4, declared in prf_dotlink.h, which this header includes here; prf_scan_stats.path = 9 is theirs. */
+#include "prf_dotlink.h"
+
 #ifdef __cplusplus
 }
 #endif

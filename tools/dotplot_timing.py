@@ -14,8 +14,14 @@ kernel.  They are counting calls (no destination): the time is the kernels', wha
 The chains cases (prf_dotpair_chains; the third field is min_seed, the fifth max_gap) count the chains that start in the
 same 2^16 x 2^16 window at (11, 8) and (16, 64) on either strand, without a min_len, so that every head is a chain; the runs cases
 at min_len 11 and 16 are their yardstick.  They report the seeds and the event times of the seed kernels and of the chain kernels.
+The links cases (prf_dotpair_links; the sixth field is max_shift) count the junctions into the chains that start in the
+same window at (11, 8, 4) and (16, 64, 32) on either strand; the chains cases are their yardstick.  The stand-in has almost no
+diverged copies, so the join kernel mostly finds no candidate there: links-synth and chains-synth run the same calls on two
+loaded sequences of 2^16 letters, the second a copy of the first with a base changed every 20 to 30 letters and a base inserted
+or removed every 60 to 100, so that step B and the emission run.  They report the heads and the event times of the seed kernels
+and of the heads and join kernels.
 
-    python3 tools/dotplot_timing.py [--length 50818468] [--runs 7] [--warmup 2] [--limit 300] [--only counts:16:3,bits:14:3:-,chains:16:11:+:8,...]
+    python3 tools/dotplot_timing.py [--length 50818468] [--runs 7] [--warmup 2] [--limit 300] [--only counts:16:3,bits:14:3:-,chains:16:11:+:8,links:16:11:+:8:4,...]
 """
 import argparse
 import json
@@ -33,6 +39,8 @@ PAIR_CASES = [(mode, log2, t, strand) for strand in "+-" for mode, log2, t in CA
               (("counts", 16, 3), ("counts", 16, 12), ("bits", 14, 3), ("bits", 14, 12))]
 RUNS_CASES = [("runs", 16, 11, "+"), ("runs", 16, 11, "-"), ("runs", 16, 32, "+"), ("runs", 16, 32, "-"), ("runs-self", 22, 64, "+")]
 CHAINS_CASES = [case for strand in "+-" for case in (("runs", 16, 16, strand), ("chains", 16, 11, strand, 8), ("chains", 16, 16, strand, 64))]
+LINKS_CASES = [case for strand in "+-" for case in (("links", 16, 11, strand, 8, 4), ("links", 16, 16, strand, 64, 32))]
+LINKS_CASES += [("chains-synth", 16, 11, "+", 8), ("links-synth", 16, 11, "+", 8, 4), ("chains-synth", 16, 16, "+", 64), ("links-synth", 16, 16, "+", 64, 32)]
 OFFSET = 30_000_000      # the window's first row and column: in the sequence, behind the stand-in's inner gap of N
 
 
@@ -92,15 +100,77 @@ def one_chains(args, genome, side, min_seed, strand, max_gap):
                       "n_seeds": stats.n_candidates, "n_heads": n.value, "n_chains": n.value}), flush=True)
 
 
+def diverged_pair(side, seed):
+    """Two sequences of `side` random letters (bytes): the second is the first with a base changed every 20 to 30 letters and a
+    base inserted or removed every 60 to 100, cut to `side` letters."""
+    import random
+    rng = random.Random(seed)
+    a = bytes(rng.choice(b"ACGT") for _ in range(side))
+    b = bytearray(a)
+    at = 0
+    while at < len(b) - 30:
+        at += rng.randrange(20, 31)
+        b[at] = b"ACGT"[(b"ACGT".index(b[at]) + 1) % 4]
+    out, at = bytearray(), 0
+    while at < len(b):
+        step = rng.randrange(60, 101)
+        out += b[at:at + step]
+        at += step
+        if rng.random() < 0.5:
+            out.append(rng.choice(b"ACGT"))
+        else:
+            at += 1
+    return a, bytes(out[:side])
+
+
+def one_links(args, genome, a, b, window, mode, min_seed, strand, max_gap, max_shift):
+    """The links cases (max_shift set) and their chains yardstick on loaded sequences (max_shift None): counting calls, both
+    directions, no destination."""
+    import ctypes
+    import prf_native
+    lib, side = genome.ctx.lib, window[1] - window[0]
+    ms, seeds_ms, rest_ms = [], [], []
+    for i in range(args.warmup + args.runs):
+        n, stats = ctypes.c_uint64(0), prf_native.ScanStats()
+        head = (genome.ctx._h, genome._h, *a, *b, prf_native.STRANDS[strand], *window, *window, 3, min_seed, max_gap)
+        if max_shift is None:
+            prf_native._check(lib, lib.prf_dotpair_chains(*head, 0, None, 0, ctypes.byref(n), ctypes.byref(stats)))
+        else:
+            prf_native._check(lib, lib.prf_dotpair_links(*head, max_shift, None, 0, ctypes.byref(n), ctypes.byref(stats)))
+        if i >= args.warmup:
+            ms.append(stats.scan_ms), seeds_ms.append(stats.phase1_ms), rest_ms.append(stats.phase2_ms)
+    med = statistics.median(ms)
+    what = "chain_kernels" if max_shift is None else "link_kernels"
+    print(json.dumps({"mode": mode, "strand": strand, "rows": side, "cols": side, "min_seed": min_seed, "max_gap": max_gap, "max_shift": max_shift,
+                      "runs": args.runs, "launches": stats.n_launches, "scan_ms_median": round(med, 4), "scan_ms_min": round(min(ms), 4),
+                      "scan_ms_max": round(max(ms), 4), "seed_kernels_ms_median": round(statistics.median(seeds_ms), 4),
+                      f"{what}_ms_median": round(statistics.median(rest_ms), 4), f"{what}_ms_max": round(max(rest_ms), 4),
+                      "cells_per_s": round(side * side / med * 1e3, 0), "n_seeds_or_heads": stats.n_candidates,
+                      "n_chains" if max_shift is None else "n_links": n.value}), flush=True)
+
+
 def one(args):
     import prf_native
     import synth  # noqa: F401
-    mode, log2, t, strand, gap = (args.case.split(":") + [None, None])[:5]
+    mode, log2, t, strand, gap, shift = (args.case.split(":") + [None, None, None])[:6]
     side, t = 1 << int(log2), int(t)
+    if mode.endswith("-synth"):
+        ctx = prf_native.Context(0)
+        genome = ctx.load(list(diverged_pair(side, args.seed)), 64)
+        one_links(args, genome, (0, 0, side), (1, 0, side), (0, side), mode, t, strand, int(gap), None if shift is None else int(shift))
+        genome.free()
+        ctx.close()
+        return
     if OFFSET + side > args.length:
         raise SystemExit(f"--length {args.length} is too short for a window of {side} positions from {OFFSET}")
     ctx = prf_native.Context(0)
     genome = ctx.standin([args.length], [args.seed], 64)
+    if mode == "links":
+        whole = (0, 0, (1 << 64) - 1)
+        one_links(args, genome, whole, whole, (OFFSET, OFFSET + side), mode, t, strand, int(gap), int(shift))
+        genome.free()
+        ctx.close()
+        return
     if mode.startswith("runs") or mode == "chains":
         one_runs(args, genome, mode, side, t, strand) if mode != "chains" else one_chains(args, genome, side, t, strand, int(gap))
         genome.free()
@@ -138,11 +208,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--limit", type=int, default=300, help="seconds per measurement (warm-up and timed calls together)")
     ap.add_argument("--only", help="comma-separated measurements to make, e.g. counts:16:3,bits:14:12 (default: all)")
-    ap.add_argument("--case", help="(internal) mode:log2 side:min_diagonal_run[:strand[:max_gap]] -- run this one measurement in this process")
+    ap.add_argument("--case", help="(internal) mode:log2 side:min_diagonal_run[:strand[:max_gap[:max_shift]]] -- run this one measurement in this process")
     args = ap.parse_args()
     if args.case:
         return one(args)
-    for case in [":".join(str(v) for v in c) for c in CASES + PAIR_CASES + RUNS_CASES + CHAINS_CASES]:
+    for case in [":".join(str(v) for v in c) for c in CASES + PAIR_CASES + RUNS_CASES + CHAINS_CASES + LINKS_CASES]:
         mode, log2, t = case.split(":")[:3]
         if args.only and case not in args.only.split(","):
             continue
