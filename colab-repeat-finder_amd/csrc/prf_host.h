@@ -269,3 +269,37 @@ struct prf_dotlink_args {
 hipError_t prf_launch_dotlink_heads(hipStream_t s, const prf_dotruns_args &a, const prf_dotlink_args &c);
 // one wave per head; n_heads = the heads' count, read by the caller
 hipError_t prf_launch_dotlink_join(hipStream_t s, const prf_dotruns_args &a, const prf_dotlink_args &c, u64 n_heads);
+
+// chains on the period lines of one range (periodchain.hip): the find kernel forms the cells of lines kmin .. kmax from
+// planes staged in LDS, finds the run starts of the window, probes, measures, tests for a head and follows; the long kernel
+// finishes, one wave per entry, what was still going after PRF_DOTCHAIN_FOLLOW cells.
+struct prf_pchain_dev {       // = prf_pchain
+    u64 start, len, matches;
+    u32 k, seeds;
+};
+struct prf_pchain_long {      // a first run (phase 0) or a chain (phase 1) that is still going, with the state of its walk
+    u64 t0;                   // the first seed's first cell
+    u64 end, matches, pending, p, run_start;   // dc_state; phase 0: p only, the next cell of the run to look at
+    u32 k, seeds, in_run, phase;
+};
+enum { PRF_PC_CHAINS = 0, PRF_PC_LONG = 1, PRF_PC_SEEDS = 2, PRF_PC_N = 3 };   // chains found, entries of the long list, seeds of the window
+struct prf_periodchain_args {
+    prf_planes pl;
+    u64 g_begin, n;           // the range: n positions from global position g_begin
+    u64 n_words;              // ceil(n / 64)
+    u64 pos0, pos1;           // the window of starts (clipped to n)
+    u64 word0, word1;         // words of the range this launch looks for starts in
+    u32 kmin, kmax;           // kmax < n
+    u32 n_matches, max_gap;
+    u64 min_seed, min_len;
+    prf_pchain_dev *dst;      // `capacity` rows; chains behind them are counted, not written
+    u64 capacity;
+    prf_pchain_long *longs;
+    u64 long_cap;
+    u64 *counters;            // PRF_PC_N words, zeroed by the caller
+    u32 span_words, kslice, lds_stride;   // set by the launch wrapper (prf_periodchain_shape)
+};
+void prf_periodchain_shape(bool exotic, u32 *span_words, u32 *kslice, u32 *lds_stride);
+hipError_t prf_launch_periodchain_find(hipStream_t s, prf_periodchain_args a);
+// one wave per entry of the long list; n_long = the list's count (<= long_cap), read by the caller
+hipError_t prf_launch_periodchain_long(hipStream_t s, const prf_periodchain_args &a, u64 n_long);

@@ -6,6 +6,9 @@ Beyond the reference: the input may be a FASTA file with -i chrom:start-end, and
 periodicity profile -- for every period k and every window of W positions, the number of positions that match their k-th
 neighbour -- which has no size limit (a chromosome takes well under a second on the device):
     plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --window 65536 --tsv profile.tsv
+--chains-tsv lists the DIVERGED TANDEM REPEATS of the input instead: on every period line, exact runs of at least --min-seed
+positions joined across at most --max-gap mismatching ones; it needs neither --window nor an image:
+    plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --chains-tsv repeats.tsv --min-seed 12 --max-gap 8
 """
 import argparse
 import os
@@ -26,7 +29,43 @@ def build_parser():
                                               "positions (a multiple of 64). Needed above 5,000 positions.")
     p.add_argument("--tsv", help="With --window: also write the profile as a table: chrom, start, end, k, matches; one line per "
                                  "(window, k) with at least one match.")
+    p.add_argument("--chains-tsv", help="List the diverged tandem repeats instead of plotting: one line per repeat with chrom, "
+                                        "start, end, k, copies, identity, matches, seeds and the first k bases. Needs --min-seed "
+                                        "and --max-gap; no image is written.")
+    p.add_argument("--min-seed", type=int, help="With --chains-tsv: positions an exact run must match its k-th neighbour to count.")
+    p.add_argument("--max-gap", type=int, help="With --chains-tsv: mismatching positions two runs are joined across (0 .. 4096).")
+    p.add_argument("--min-chain", type=int, default=0, help="With --chains-tsv: keep repeats of at least this many cells "
+                                                            "(end - start - k).")
+    p.add_argument("--min-identity", type=float, default=0.0, help="With --chains-tsv: keep repeats of at least this identity.")
+    p.add_argument("--keep-multiples", action="store_true", help="With --chains-tsv: keep the images of a repeat at multiples of "
+                                                                 "its period.")
+    p.add_argument("--n-matches", action="store_true", help="With --chains-tsv: N matches N, as in the matrix (default: N never "
+                                                            "matches, as in the scans).")
+    p.add_argument("--chain-window", type=int, default=1 << 22, help="With --chains-tsv: start positions per call.")
     return p
+
+
+def check_chain_args(args, parser):
+    """The checks of the --chains-tsv arguments, which need no GPU."""
+    if not args.chains_tsv:
+        for name in ("min_seed", "max_gap"):
+            if getattr(args, name) is not None:
+                parser.error(f"--{name.replace('_', '-')} belongs to --chains-tsv")
+        return
+    if args.min_seed is None or args.max_gap is None:
+        parser.error("--chains-tsv needs --min-seed and --max-gap")
+    if args.min_seed < 1:
+        parser.error(f"--min-seed is set to {args.min_seed}. It must be at least 1.")
+    if not 0 <= args.max_gap <= 4096:
+        parser.error(f"--max-gap is set to {args.max_gap}. It must be 0 .. 4096.")
+    if args.min_chain < 0:
+        parser.error(f"--min-chain is set to {args.min_chain}. It must be at least 0.")
+    if not 0.0 <= args.min_identity <= 1.0:
+        parser.error(f"--min-identity is set to {args.min_identity}. It must be 0 .. 1.")
+    if args.chain_window < 1:
+        parser.error(f"--chain-window is set to {args.chain_window}. It must be at least 1.")
+    if args.window is not None or args.tsv:
+        parser.error("--chains-tsv lists repeats; --window and --tsv belong to the profile")
 
 
 def resolve_input(args, parser):
@@ -37,6 +76,7 @@ def resolve_input(args, parser):
         parser.error(f"--max-motif-size is set to {args.max_motif_size}. It must be at least --min-motif-size.")
     if args.window is not None and (args.window < 64 or args.window % 64):
         parser.error(f"--window is set to {args.window}. It must be a multiple of 64, at least 64.")
+    check_chain_args(args, parser)
     if args.tsv and args.window is None:
         parser.error("--tsv writes the windowed profile: give --window too")
     if os.path.isfile(args.input_sequence):
@@ -60,7 +100,7 @@ def resolve_input(args, parser):
         if not args.input_sequence.isalpha():
             parser.error(f"Invalid input: {args.input_sequence}. This should be a FASTA file path or a string of letters.")
         chrom, seq, begin, end = "sequence", args.input_sequence, 0, len(args.input_sequence)
-    if args.window is None and end - begin > MAX_MATRIX_POSITIONS:
+    if args.window is None and not args.chains_tsv and end - begin > MAX_MATRIX_POSITIONS:
         parser.error(f"The input sequence is too long for the full matrix ({end - begin:,d} bp > {MAX_MATRIX_POSITIONS:,d}). "
                      f"Use --window W (a multiple of 64) to plot the periodicity profile instead.")
     return chrom, seq, begin, end
@@ -75,10 +115,39 @@ def profile_lines(chrom, begin, end, window, min_motif_size, counts):
             yield f"{chrom}\t{start}\t{stop}\t{min_motif_size + r}\t{int(counts[r, w])}\n"
 
 
-def main(argv=None):
+def chain_lines(chrom, begin, seq, rows):
+    """The --chains-tsv lines of the rows of prf_native.tandem_rows, whose positions are relative to begin."""
+    for start, stop, k, copies, identity, matches, seeds in rows.tolist():
+        yield (f"{chrom}\t{begin + start}\t{begin + stop}\t{k}\t{copies:.3f}\t{identity:.4f}\t{matches}\t{seeds}\t"
+               f"{seq[begin + start:begin + start + k].upper()}\n")
+
+
+def list_chains(args, chrom, seq, begin, end, context=None):
+    """--chains-tsv: the interval in windows of --chain-window start positions, the lists concatenated."""
+    import numpy as np
+    import prf_native
+    ctx = context if context is not None else prf_native.default_context()
+    genome = ctx.load([seq.encode("ascii", "replace")], 64)
+    try:
+        parts = [genome.period_chains(0, begin, end, args.min_motif_size, args.max_motif_size, args.min_seed, args.max_gap,
+                                      args.min_chain, args.n_matches, (at, min(at + args.chain_window, end - begin)))
+                 for at in range(0, end - begin, args.chain_window)]
+    finally:
+        genome.free()
+    chains = np.concatenate(parts) if parts else np.zeros(0, dtype=prf_native.PCHAIN_DTYPE)
+    rows = prf_native.tandem_rows(chains, drop_multiples=not args.keep_multiples)
+    rows = rows[rows["identity"] >= args.min_identity]
+    with open(args.chains_tsv, "wt") as out:
+        out.writelines(chain_lines(chrom, begin, seq, rows))
+    print(f"Wrote {args.chains_tsv}: {len(rows)} repeats")
+
+
+def main(argv=None, context=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     chrom, seq, begin, end = resolve_input(args, parser)
+    if args.chains_tsv:
+        return list_chains(args, chrom, seq, begin, end, context)
     from utils.plot_utils import get_period_matrix, plot_periodicity_matrix
     if args.window is None:
         matrix = get_period_matrix(args.min_motif_size, args.max_motif_size, seq[begin:end])

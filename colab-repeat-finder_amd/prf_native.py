@@ -150,6 +150,16 @@ DOTLINK_DEFAULT_CAPACITY = 1 << 16   # rows the first of the binding's two calls
 DOTGROUP_DTYPE = [("row", "<u8"), ("col", "<u8"), ("end_row", "<u8"), ("end_col", "<u8"), ("span_a", "<u8"), ("span_b", "<u8"),
                   ("matches", "<u8"), ("gap_cells", "<u8"), ("dir", "<u4"), ("chains", "<u4"), ("seeds", "<u4"), ("indel", "<u4"),
                   ("open", "?")]
+# the entry points of the list of diverged tandem repeats: chains on the period lines of one range (include/prf_periodchain.h,
+# which prf.h includes)
+PERIODCHAIN_EXPORTS = ["prf_period_chains", "prf_period_chains_ex", "prf_period_chains_seq"]
+PCHAIN_DTYPE = [("start", "<u8"), ("len", "<u8"), ("matches", "<u8"), ("k", "<u4"), ("seeds", "<u4")]   # prf_pchain, 32 bytes
+PCHAIN_MAX_ROWS = 1 << 24            # PRF_PCHAIN_MAX_ROWS
+PCHAIN_LONG_ROWS = 1 << 20           # PRF_PCHAIN_LONG_ROWS
+PCHAIN_DEFAULT_CAPACITY = 1 << 16    # rows the first of the binding's two calls has room for
+# one row of tandem_rows per repeat
+TANDEM_DTYPE = [("start", "<u8"), ("end", "<u8"), ("k", "<u4"), ("copies", "<f8"), ("identity", "<f8"), ("matches", "<u8"),
+                ("seeds", "<u4")]
 DIRECTIONS = {"main": 1, "anti": 2, "both": 3}
 DOT_LAUNCH_CELLS = 1 << 36   # PRF_DOT_LAUNCH_CELLS
 DOT_MAX_CELLS = 1 << 42      # PRF_DOT_MAX_CELLS
@@ -273,6 +283,12 @@ def load_library():
         lib.prf_dotpair_links.argtypes = on_genome[:-6] + links_tail
         lib.prf_dotpair_links_ex.argtypes = on_genome[:-6] + links_tail + [ctypes.c_uint64]
         lib.prf_dotpair_links_seq.argtypes = one_shot[:-6] + links_tail
+        # begin, end, pos0, pos1, kmin, kmax, n_matches, min_seed, max_gap, min_len, dst, capacity, n_chains, stats
+        pchains_tail = [ctypes.c_uint64] * 4 + [ctypes.c_uint32] * 3 + [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, vp,
+                                                                        ctypes.c_uint64, u64p, ctypes.POINTER(ScanStats)]
+        lib.prf_period_chains.argtypes = [vp, vp, ctypes.c_uint32] + pchains_tail
+        lib.prf_period_chains_ex.argtypes = [vp, vp, ctypes.c_uint32] + pchains_tail + [ctypes.c_uint64]
+        lib.prf_period_chains_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + pchains_tail
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
         lib.prf_measure_hbm_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -592,6 +608,72 @@ def _links(ctx, a_target, a_range, b_target, b_range, strand, directions, min_se
     return (links, stats) if with_stats else links
 
 
+def _period_chains(ctx, target, begin, end, kmin, kmax, min_seed, max_gap, min_len, n_matches, positions, with_stats, launch_cells):
+    """The one path of the period_chains calls, as _chains: target is (genome, contig) or one sequence; once with
+    PCHAIN_DEFAULT_CAPACITY rows of room and once more with the exact number if there were more."""
+    import numpy as np
+    if isinstance(kmin, bool) or isinstance(kmax, bool) or not 1 <= operator.index(kmin) <= operator.index(kmax) <= 0xFFFFFFFF:
+        raise ValueError(f"periods {kmin} .. {kmax}: an empty range")
+    if isinstance(min_seed, bool) or operator.index(min_seed) < 1:
+        raise ValueError(f"min_seed is set to {min_seed}. It must be at least 1.")
+    if isinstance(max_gap, bool) or not 0 <= operator.index(max_gap) <= DOTCHAIN_MAX_GAP:
+        raise ValueError(f"max_gap is set to {max_gap}. It must be 0 .. {DOTCHAIN_MAX_GAP}.")
+    if isinstance(min_len, bool) or operator.index(min_len) < 0:
+        raise ValueError(f"min_len is set to {min_len}. It must be at least 0.")
+    lo, hi = (0, None) if positions is None else positions
+    if lo < 0 or (hi is not None and lo > hi):
+        raise ValueError(f"positions {lo} .. {hi}: an empty range is given as lo == hi")
+    where, _n, c_end, keep = _matrix_range(target, begin, end)
+    args = where + (begin, c_end, lo, END_OF_CONTIG if hi is None else hi, kmin, kmax, 1 if n_matches else 0, min_seed, max_gap, min_len)
+    if keep is not None:
+        fn, head, tail = ctx.lib.prf_period_chains_seq, (ctx._h,), ()
+    else:
+        fn, head, tail = ctx.lib.prf_period_chains_ex, (ctx._h, target[0]._h), (launch_cells,)
+    capacity = PCHAIN_DEFAULT_CAPACITY
+    while True:
+        out = np.zeros(max(1, capacity), dtype=PCHAIN_DTYPE)
+        n, stats = ctypes.c_uint64(0), ScanStats()
+        _check(ctx.lib, fn(*head, *args, out.ctypes.data_as(ctypes.c_void_p), capacity, ctypes.byref(n), ctypes.byref(stats), *tail))
+        if n.value <= capacity:
+            break
+        if n.value > PCHAIN_MAX_ROWS:
+            raise PrfError(PRF_EUNSUPPORTED, f"{n.value} chains are more than one call returns ({PCHAIN_MAX_ROWS}): ask for a larger "
+                                             "min_seed or min_len, fewer periods or fewer positions")
+        capacity = n.value
+    chains = out[:n.value].copy()
+    return (chains, stats) if with_stats else chains
+
+
+def tandem_rows(chains, drop_multiples=True):
+    """The repeats of a list of period_chains, one row of TANDEM_DTYPE each, in the list's order: start, end = start + len + k (the
+    positions the repeat covers), k, copies = (len + k) / k, identity = matches / len, matches, seeds.  A repeat of period 3 is
+    also periodic at 6, 9, ...: drop_multiples removes a row (k, [a, b)) iff another row (k', [a', b')) of the list has k' < k,
+    k % k' == 0, a' <= a and b' >= b.  Host numpy."""
+    import numpy as np
+    out = np.zeros(len(chains), dtype=TANDEM_DTYPE)
+    k = chains["k"].astype(np.uint64)
+    out["start"], out["k"], out["matches"], out["seeds"] = chains["start"], chains["k"], chains["matches"], chains["seeds"]
+    out["end"] = chains["start"] + chains["len"] + k
+    out["copies"] = (chains["len"] + k).astype(np.float64) / np.maximum(k, 1).astype(np.float64)
+    out["identity"] = chains["matches"].astype(np.float64) / np.maximum(chains["len"], 1).astype(np.float64)
+    if not drop_multiples or len(out) < 2:
+        return out
+    # by start, longest first: a row can only lie inside a row in front of it; the rows in front that can still hold a later one
+    # are kept per period, as the largest end seen so far
+    order = np.lexsort((out["k"], -out["end"].astype(np.int64), out["start"].astype(np.int64)))
+    keep = np.ones(len(out), dtype=bool)
+    reach, divisors = {}, {}                                    # period -> the largest end of the rows in front; -> its proper divisors
+    for at, kk, b in zip(order.tolist(), out["k"][order].tolist(), out["end"][order].tolist()):
+        if kk not in divisors:
+            small = [q for q in range(1, int(kk ** 0.5) + 1) if kk % q == 0]
+            divisors[kk] = sorted({q for d in small for q in (d, kk // d) if q < kk})
+        if any(reach.get(q, 0) >= b for q in divisors[kk]):
+            keep[at] = False
+        if reach.get(kk, 0) < b:
+            reach[kk] = b
+    return out[keep]
+
+
 def join_chains(chains, links, nb=None):
     """The gapped repeats of a window: the chains of dotpair_chains (fetched at min_len = 0) joined along the links of
     dotpair_links of the same window, min_seed and max_gap.  Every chain has at most one link in and one out, so the links form
@@ -767,6 +849,18 @@ class Genome:
         repeats."""
         return _links(self.ctx, (self, a[0]), a[1:], (self, b[0]), b[1:], strand, directions, min_seed, max_gap, max_shift, rows, cols,
                       with_stats, launch_cells)
+
+    def period_chains(self, contig, begin, end, kmin, kmax, min_seed, max_gap, min_len=0, n_matches=False, positions=None,
+                      with_stats=False, launch_cells=0):
+        """The DIVERGED TANDEM REPEATS of positions [begin, end) of a contig (prf_period_chains): on every period line k = kmin ..
+        kmax of the range (cell t: seq[t] == seq[t + k], t + k < end) the exact runs of at least min_seed cells, joined wherever
+        at most max_gap cells lie between two of them.  A numpy structured array with the fields start (relative to begin), len,
+        matches, k and seeds, sorted by (start, k): the chains that start in positions = (pos0, pos1) (None: all) and have at least
+        min_len cells; the repeat covers [start, start + len + k).  n_matches: N == N is a match, as in period_bits; False: N
+        never matches, as in the scans.  Chains are judged on the whole line: the lists of a partition in positions or in k add
+        up.  end None: the contig's end.  tandem_rows() turns the list into repeats."""
+        return _period_chains(self.ctx, (self, contig), begin, end, kmin, kmax, min_seed, max_gap, min_len, n_matches, positions,
+                              with_stats, launch_cells)
 
     @property
     def positions(self):
@@ -975,6 +1069,11 @@ class Context:
                       b=(0, None), rows=None, cols=None, with_stats=False):
         """Genome.dotpair_links for two sequences (str or bytes) in one call: load, list, free (prf_dotpair_links_seq)."""
         return _links(self, seq_a, a, seq_b, b, strand, directions, min_seed, max_gap, max_shift, rows, cols, with_stats, 0)
+
+    def period_chains(self, seq, kmin, kmax, min_seed, max_gap, min_len=0, n_matches=False, begin=0, end=None, positions=None,
+                      with_stats=False):
+        """Genome.period_chains for one sequence (str or bytes) in one call: load, list, free (prf_period_chains_seq)."""
+        return _period_chains(self, seq, begin, end, kmin, kmax, min_seed, max_gap, min_len, n_matches, positions, with_stats, 0)
 
     def period_counts(self, seq, kmin, kmax, window, begin=0, end=None, with_stats=False):
         """Genome.period_counts for one sequence (str or bytes) in one call: load, count, free (prf_period_counts_seq)."""

@@ -350,6 +350,10 @@ int prf_measure_hbm_read(prf_ctx *ctx, uint64_t bytes, int iters, double *gbps);
  * ABI version 4, declared in prf_dotlink.h, which this header includes here; prf_scan_stats.path = 9 is theirs. */
 #include "prf_dotlink.h"
 
+/* ---- the diverged tandem repeats of a range: chains on the period lines k = kmin .. kmax: three more entry points,
+ * additions to ABI version 4, declared in prf_periodchain.h, which this header includes here; prf_scan_stats.path = 10 is theirs. */
+#include "prf_periodchain.h"
+
 #ifdef __cplusplus
 }
 #endif
