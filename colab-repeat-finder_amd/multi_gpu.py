@@ -102,12 +102,14 @@ def unpack_rows(words, capacity, side_capacity, bases, tile):
 
 
 WIRE_K_MAX = 511   # motif sizes the 8-byte wire row holds (9 bits); larger ones are refused by the library (PRF_EUNSUPPORTED)
+WIRE_POSITIONS = 1 << 39   # global positions the 8-byte wire row addresses: 23 bits of tile, 16 bits of start in the tile
 
 
 def pack_rows(rows, capacity, side_capacity, bases, tile):
     """Host reference encoder of the 8-byte wire format (what prf_pack_rows_kernel, csrc/verify.hip, writes on the device;
     a GPU test checks the two against each other): `capacity` packed rows, one count word (rows | long rows << 40),
-    3 * side_capacity words of rows whose span does not fit 16 bits.  Returns a uint64 array."""
+    3 * side_capacity words of rows whose span does not fit 16 bits.  Returns a uint64 array.  A row whose first global position
+    is WIRE_POSITIONS (2^39) or more does not fit the tile field: ValueError (a genome may hold 2^40 positions)."""
     rows = np.asarray(rows, dtype=ROW_DTYPE)
     n = len(rows)
     if n > capacity:
@@ -117,6 +119,8 @@ def pack_rows(rows, capacity, side_capacity, bases, tile):
     words = np.zeros(capacity + 1 + 3 * side_capacity, dtype=np.uint64)
     bases = np.asarray(bases, dtype=np.uint64)
     gpos = bases[rows["contig"]] + rows["start"]
+    if n and int(gpos.max()) >= WIRE_POSITIONS:
+        raise ValueError(f"global position {int(gpos.max())} does not fit the 8-byte wire row, which addresses 2^39 positions")
     span = rows["end"] - rows["start"]
     s16 = np.minimum(span, np.uint64(65535))
     words[:n] = ((gpos // np.uint64(tile)) << np.uint64(41)) | ((gpos % np.uint64(tile)) << np.uint64(25)) | (s16 << np.uint64(9)) \

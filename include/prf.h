@@ -270,6 +270,9 @@ int prf_last_hits_to_device(prf_ctx *ctx, void *dst_device, uint64_t capacity_ro
 /* The same hand-off in the 8-byte wire format of the multi-GPU gather (a third of the bytes on the xGMI links): word i =
  * tile << 41 | start in the tile << 25 | min(end - start, 65535) << 9 | k, where tile * prf_tile_positions() + start in the
  * tile is the row's first position in the genome's coordinate space (contig c begins at prf_genome_contig_bases()[c]).
+ * The tile has 23 bits, so the packed hand-off addresses 2^39 positions, half of what prf_genome_load accepts (2^40): a
+ * resident genome of that size does not fit the device's memory, and the host encoder multi_gpu.pack_rows() refuses a row at
+ * or beyond global position 2^39 with ValueError.
  * dst_device holds capacity_rows words, then ONE count word (rows | long rows << 40), then side_capacity full rows of three
  * words (start, end, k | contig << 32) for the rows whose span does not fit 16 bits.  multi_gpu.unpack_rows() decodes.
  * Fails with PRF_EINVAL if the scan found more rows than capacity_rows (or more long rows than side_capacity), and with
