@@ -4,11 +4,12 @@
 //   1. the find kernel over the words of the window, cut into launches of at most launch_cells cells: rows, or entries of the
 //      long list;
 //   2. the long kernel for the first runs and chains the find kernel left, one wave each.
-// The rows are copied and sorted here.  No selection is read, no row sink written, the last scan's rows stay.
+// Both are the stage of periodchain_stage.h, which leaves the rows on the device (periodlink_host.cpp goes on from there).  The
+// rows are copied and sorted here.  No selection is read, no row sink written, the last scan's rows stay.
 #include <algorithm>
 #include <vector>
 
-#include "matrix_host.h"
+#include "periodchain_stage.h"
 
 namespace {
 
@@ -24,10 +25,7 @@ struct pchains_request {
     u64 capacity;
     uint64_t *n_chains;
     u64 launch_cells;   // 0: PRF_DOT_LAUNCH_CELLS
-    struct room {
-        u64 n;              // positions of the clipped range
-        u64 pos0, pos1;     // the clipped window
-    };
+    using room = pchain_room;
 
     int check(const char *name) const {
         if (begin > end) return fail(PRF_EINVAL, "%s: begin %llu is behind end %llu", name, (unsigned long long)begin, (unsigned long long)end);
@@ -47,15 +45,7 @@ struct pchains_request {
     }
 
     int check_room(const char *name, u64 seq_len, room *o) const {
-        const int rc = matrix_clip(name, begin, end, seq_len, &o->n);
-        if (rc) return rc;
-        o->pos1 = pos1 < o->n ? pos1 : o->n;
-        o->pos0 = pos0 < o->pos1 ? pos0 : o->pos1;
-        const u64 starts = o->pos1 - o->pos0, nk = (u64)kmax - kmin + 1;
-        if (starts && nk > PRF_DOT_MAX_CELLS / starts)
-            return fail(PRF_EUNSUPPORTED, "%s: a window of %llu positions x %llu lines is above the limit of 2^42 cells per call (PRF_DOT_MAX_CELLS)",
-                        name, (unsigned long long)starts, (unsigned long long)nk);
-        return PRF_OK;
+        return pchain_check_room(name, begin, end, pos0, pos1, kmin, kmax, seq_len, o);
     }
 };
 
@@ -72,66 +62,12 @@ int pchains_run(const char *name, prf_ctx *c, const prf_genome *g, u32 contig, c
     float ms = 0, ms_long = 0;
     u32 launches = 0;
     u64 cnt[PRF_PC_N] = {0, 0, 0};
-    const u64 starts = o.pos1 - o.pos0;
-    if (starts && (u64)r.kmin < o.n) {                         // a line k >= n is empty
-        prf_periodchain_args a{};
-        a.pl = v.planes;
-        a.g_begin = v.base + r.begin;
-        a.n = o.n;
-        a.n_words = (o.n + 63) / 64;
-        a.pos0 = o.pos0;
-        a.pos1 = o.pos1;
-        a.kmin = r.kmin;
-        a.kmax = (u64)r.kmax < o.n ? r.kmax : (u32)(o.n - 1);
-        a.n_matches = r.n_matches;
-        a.max_gap = r.max_gap;
-        a.min_seed = r.min_seed;
-        a.min_len = r.min_len;
-        a.capacity = r.capacity;
-        const u64 nk = (u64)a.kmax - a.kmin + 1;
-        // two heads of one line lie more than PRF_DOTCHAIN_FOLLOW cells apart if the first one is still going there
-        const u64 most_long = nk * (starts / PRF_DOTCHAIN_FOLLOW + 2);
-        a.long_cap = most_long < PRF_PCHAIN_LONG_ROWS ? most_long : PRF_PCHAIN_LONG_ROWS;
+    if (pchain_any(o, r.kmin)) {
+        const prf_periodchain_args a = pchain_args(v, o, r.begin, r.kmin, r.kmax, r.n_matches, r.min_seed, r.max_gap, r.min_len);
         dev_array<prf_pchain_dev> d_out;
         dev_array<prf_pchain_long> d_long;
         dev_array<u64> d_cnt;
-        if ((rc = d_out.alloc(a.capacity)) || (rc = d_long.alloc(a.long_cap)) || (rc = d_cnt.alloc(PRF_PC_N))) return rc;
-        a.dst = d_out.p;
-        a.longs = d_long.p;
-        a.counters = d_cnt.p;
-        HIPCHK(hipMemsetAsync(d_cnt.p, 0, PRF_PC_N * sizeof(u64), c->stream));
-        // ---- 1. the words of the window, whole spans per launch
-        u32 span_words, kslice, stride;
-        prf_periodchain_shape(a.pl.E[0] != nullptr, &span_words, &kslice, &stride);
-        const u64 cells = r.launch_cells ? r.launch_cells : PRF_DOT_LAUNCH_CELLS;
-        u64 spans = cells / nk / 64 / span_words;
-        if (spans < 1) spans = 1;
-        if (spans > (1ull << 30)) spans = 1ull << 30;
-        const u64 w_end = (o.pos1 + 63) / 64;
-        HIPCHK(hipEventRecord(c->ev[0], c->stream));
-        for (u64 w = o.pos0 / 64; w < w_end; w += spans * span_words) {
-            a.word0 = w;
-            a.word1 = w_end - w > spans * span_words ? w + spans * span_words : w_end;
-            HIPCHK(prf_launch_periodchain_find(c->stream, a));
-            ++launches;
-        }
-        HIPCHK(hipEventRecord(c->ev[1], c->stream));
-        HIPCHK(hipMemcpyAsync(cnt, d_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        if (cnt[PRF_PC_LONG] > a.long_cap)
-            return fail(PRF_EUNSUPPORTED, "%s: %llu runs and chains are still going %u cells (PRF_DOTCHAIN_FOLLOW) behind their start, the call keeps room for %llu: ask for a smaller window",
-                        name, (unsigned long long)cnt[PRF_PC_LONG], PRF_DOTCHAIN_FOLLOW, (unsigned long long)a.long_cap);
-        // ---- 2. what the find kernel left
-        if (cnt[PRF_PC_LONG]) {
-            HIPCHK(hipEventRecord(c->ev[0], c->stream));
-            HIPCHK(prf_launch_periodchain_long(c->stream, a, cnt[PRF_PC_LONG]));
-            ++launches;
-            HIPCHK(hipEventRecord(c->ev[1], c->stream));
-            HIPCHK(hipMemcpyAsync(cnt, d_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            HIPCHK(hipEventElapsedTime(&ms_long, c->ev[0], c->ev[1]));
-        }
+        if ((rc = pchain_rows(name, c, a, r.launch_cells, r.capacity, d_out, d_long, d_cnt, cnt, &ms, &ms_long, &launches))) return rc;
         const u64 n_chains = cnt[PRF_PC_CHAINS];
         if (n_chains && n_chains <= r.capacity) {
             std::vector<prf_pchain> got(n_chains);

@@ -1,0 +1,106 @@
+// periodchain_stage.h -- what the two host paths that work on the CHAINS of a window of period lines share (periodchain_host.cpp,
+// DESIGN 16; periodlink_host.cpp; nobody else includes it): the clipped range and window, the arguments of the kernels
+// of periodchain.hip, and the stage that runs them and leaves the rows on the device.  Moved here unchanged from
+// periodchain_host.cpp:
+//   1. the find kernel over the words of the window, cut into launches of at most launch_cells cells: rows, or entries of the
+//      long list;
+//   2. the long kernel for the first runs and chains the find kernel left, one wave each.
+#pragma once
+#include "matrix_host.h"
+
+namespace {
+
+struct pchain_room {
+    u64 n;              // positions of the clipped range
+    u64 pos0, pos1;     // the clipped window
+};
+
+int pchain_check_room(const char *name, u64 begin, u64 end, u64 pos0, u64 pos1, u32 kmin, u32 kmax, u64 seq_len, pchain_room *o) {
+    const int rc = matrix_clip(name, begin, end, seq_len, &o->n);
+    if (rc) return rc;
+    o->pos1 = pos1 < o->n ? pos1 : o->n;
+    o->pos0 = pos0 < o->pos1 ? pos0 : o->pos1;
+    const u64 starts = o->pos1 - o->pos0, nk = (u64)kmax - kmin + 1;
+    if (starts && nk > PRF_DOT_MAX_CELLS / starts)
+        return fail(PRF_EUNSUPPORTED, "%s: a window of %llu positions x %llu lines is above the limit of 2^42 cells per call (PRF_DOT_MAX_CELLS)",
+                    name, (unsigned long long)starts, (unsigned long long)nk);
+    return PRF_OK;
+}
+
+// a window with starts and lines: a line k >= n is empty
+bool pchain_any(const pchain_room &o, u32 kmin) { return o.pos1 > o.pos0 && (u64)kmin < o.n; }
+
+// the kernels' arguments for such a window; dst, capacity, longs and counters are the stage's
+prf_periodchain_args pchain_args(const prf_contig_view &v, const pchain_room &o, u64 begin, u32 kmin, u32 kmax, u32 n_matches, u64 min_seed,
+                                 u32 max_gap, u64 min_len) {
+    prf_periodchain_args a{};
+    a.pl = v.planes;
+    a.g_begin = v.base + begin;
+    a.n = o.n;
+    a.n_words = (o.n + 63) / 64;
+    a.pos0 = o.pos0;
+    a.pos1 = o.pos1;
+    a.kmin = kmin;
+    a.kmax = (u64)kmax < o.n ? kmax : (u32)(o.n - 1);
+    a.n_matches = n_matches;
+    a.max_gap = max_gap;
+    a.min_seed = min_seed;
+    a.min_len = min_len;
+    const u64 nk = (u64)a.kmax - a.kmin + 1, starts = o.pos1 - o.pos0;
+    // two heads of one line lie more than PRF_DOTCHAIN_FOLLOW cells apart if the first one is still going there
+    const u64 most_long = nk * (starts / PRF_DOTCHAIN_FOLLOW + 2);
+    a.long_cap = most_long < PRF_PCHAIN_LONG_ROWS ? most_long : PRF_PCHAIN_LONG_ROWS;
+    return a;
+}
+
+// The chains of the window into d_out (room for `cap` rows), which stay on the device: cnt[PRF_PC_CHAINS] is their number, and
+// they were all written only if it is at most cap.  *ms (the find kernel's), *ms_long and *launches are added to.
+int pchain_rows(const char *name, prf_ctx *c, prf_periodchain_args a, u64 launch_cells, u64 cap, dev_array<prf_pchain_dev> &d_out,
+                dev_array<prf_pchain_long> &d_long, dev_array<u64> &d_cnt, u64 *cnt, float *ms, float *ms_long, u32 *launches) {
+    int rc;
+    a.capacity = cap;
+    if ((rc = d_out.alloc(a.capacity)) || (rc = d_long.alloc(a.long_cap)) || (rc = d_cnt.alloc(PRF_PC_N))) return rc;
+    a.dst = d_out.p;
+    a.longs = d_long.p;
+    a.counters = d_cnt.p;
+    HIPCHK(hipMemsetAsync(d_cnt.p, 0, PRF_PC_N * sizeof(u64), c->stream));
+    // ---- 1. the words of the window, whole spans per launch
+    const u64 nk = (u64)a.kmax - a.kmin + 1;
+    u32 span_words, kslice, stride;
+    prf_periodchain_shape(a.pl.E[0] != nullptr, &span_words, &kslice, &stride);
+    const u64 cells = launch_cells ? launch_cells : PRF_DOT_LAUNCH_CELLS;
+    u64 spans = cells / nk / 64 / span_words;
+    if (spans < 1) spans = 1;
+    if (spans > (1ull << 30)) spans = 1ull << 30;
+    const u64 w_end = (a.pos1 + 63) / 64;
+    float part = 0;
+    HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    for (u64 w = a.pos0 / 64; w < w_end; w += spans * span_words) {
+        a.word0 = w;
+        a.word1 = w_end - w > spans * span_words ? w + spans * span_words : w_end;
+        HIPCHK(prf_launch_periodchain_find(c->stream, a));
+        ++*launches;
+    }
+    HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    HIPCHK(hipMemcpyAsync(cnt, d_cnt.p, PRF_PC_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipEventElapsedTime(&part, c->ev[0], c->ev[1]));
+    *ms += part;
+    if (cnt[PRF_PC_LONG] > a.long_cap)
+        return fail(PRF_EUNSUPPORTED, "%s: %llu runs and chains are still going %u cells (PRF_DOTCHAIN_FOLLOW) behind their start, the call keeps room for %llu: ask for a smaller window",
+                    name, (unsigned long long)cnt[PRF_PC_LONG], PRF_DOTCHAIN_FOLLOW, (unsigned long long)a.long_cap);
+    // ---- 2. what the find kernel left
+    if (cnt[PRF_PC_LONG]) {
+        HIPCHK(hipEventRecord(c->ev[0], c->stream));
+        HIPCHK(prf_launch_periodchain_long(c->stream, a, cnt[PRF_PC_LONG]));
+        ++*launches;
+        HIPCHK(hipEventRecord(c->ev[1], c->stream));
+        HIPCHK(hipMemcpyAsync(cnt, d_cnt.p, PRF_PC_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipEventElapsedTime(&part, c->ev[0], c->ev[1]));
+        *ms_long += part;
+    }
+    return PRF_OK;
+}
+
+}  // namespace

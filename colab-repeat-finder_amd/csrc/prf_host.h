@@ -303,3 +303,25 @@ void prf_periodchain_shape(bool exotic, u32 *span_words, u32 *kslice, u32 *lds_s
 hipError_t prf_launch_periodchain_find(hipStream_t s, prf_periodchain_args a);
 // one wave per entry of the long list; n_long = the list's count (<= long_cap), read by the caller
 hipError_t prf_launch_periodchain_long(hipStream_t s, const prf_periodchain_args &a, u64 n_long);
+
+// junctions between those chains across neighbouring period lines (periodlink.hip).  The heads are the rows the two
+// kernels above wrote at min_len = 0, left on the device; the join kernel judges one head per wave against ALL lines 1 .. n - 1.
+struct prf_plink_dev {        // = prf_plink
+    u64 start, from_end;
+    u32 k;
+    int shift;
+    u32 gap, overlap;
+};
+struct prf_periodlink_args {
+    prf_planes pl;
+    u64 g_begin, n;           // the range, as prf_periodchain_args
+    u32 n_matches, max_gap, max_shift;
+    u64 min_seed;
+    const prf_pchain_dev *heads;   // n_heads rows: the chains that start in the window, in no order
+    u64 n_heads;
+    prf_plink_dev *dst;       // `capacity` rows; links behind them are counted, not written
+    u64 capacity;
+    u64 *counter;             // one word, zeroed by the caller: links found
+};
+// one wave per head
+hipError_t prf_launch_periodlink_join(hipStream_t s, const prf_periodlink_args &a);

@@ -9,6 +9,9 @@ neighbour -- which has no size limit (a chromosome takes well under a second on 
 --chains-tsv lists the DIVERGED TANDEM REPEATS of the input instead: on every period line, exact runs of at least --min-seed
 positions joined across at most --max-gap mismatching ones; it needs neither --window nor an image:
     plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --chains-tsv repeats.tsv --min-seed 12 --max-gap 8
+--groups-tsv lists the GAPPED tandem repeats: those chains joined across indels of at most --max-shift bases (the junctions
+between neighbouring period lines), one line per repeat with substitutions and indels:
+    plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --groups-tsv vntr.tsv --min-seed 12 --max-gap 8 --max-shift 4
 """
 import argparse
 import os
@@ -32,27 +35,56 @@ def build_parser():
     p.add_argument("--chains-tsv", help="List the diverged tandem repeats instead of plotting: one line per repeat with chrom, "
                                         "start, end, k, copies, identity, matches, seeds and the first k bases. Needs --min-seed "
                                         "and --max-gap; no image is written.")
+    p.add_argument("--groups-tsv", help="List the gapped tandem repeats instead of plotting: the chains of --chains-tsv joined across "
+                                        "indels, one line per repeat with chrom, start, end, period, copies, identity, indel, "
+                                        "chains, seeds and the first `period` bases. Needs --min-seed, --max-gap and --max-shift; "
+                                        "no image is written.")
+    p.add_argument("--max-shift", type=int, help="With --groups-tsv: period lines a junction may reach: the longest indel (1 .. 32).")
+    p.add_argument("--min-group", type=int, default=0, help="With --groups-tsv: keep repeats that cover at least this many positions "
+                                                            "(end - start).")
+    p.add_argument("--keep-covered", action="store_true", help="With --groups-tsv: keep the repeats that one of a smaller period "
+                                                               "covers (the images at multiples of a period among them).")
     p.add_argument("--min-seed", type=int, help="With --chains-tsv: positions an exact run must match its k-th neighbour to count.")
     p.add_argument("--max-gap", type=int, help="With --chains-tsv: mismatching positions two runs are joined across (0 .. 4096).")
     p.add_argument("--min-chain", type=int, default=0, help="With --chains-tsv: keep repeats of at least this many cells "
                                                             "(end - start - k).")
-    p.add_argument("--min-identity", type=float, default=0.0, help="With --chains-tsv: keep repeats of at least this identity.")
+    p.add_argument("--min-identity", type=float, default=0.0, help="With --chains-tsv or --groups-tsv: keep repeats of at least this identity.")
     p.add_argument("--keep-multiples", action="store_true", help="With --chains-tsv: keep the images of a repeat at multiples of "
                                                                  "its period.")
-    p.add_argument("--n-matches", action="store_true", help="With --chains-tsv: N matches N, as in the matrix (default: N never "
+    p.add_argument("--n-matches", action="store_true", help="With --chains-tsv or --groups-tsv: N matches N, as in the matrix (default: N never "
                                                             "matches, as in the scans).")
-    p.add_argument("--chain-window", type=int, default=1 << 22, help="With --chains-tsv: start positions per call.")
+    p.add_argument("--chain-window", type=int, default=1 << 22, help="With --chains-tsv or --groups-tsv: start positions per call.")
     return p
 
 
 def check_chain_args(args, parser):
-    """The checks of the --chains-tsv arguments, which need no GPU."""
-    if not args.chains_tsv:
+    """The checks of the --chains-tsv and --groups-tsv arguments, which need no GPU."""
+    if not args.groups_tsv:
+        if args.max_shift is not None:
+            parser.error("--max-shift belongs to --groups-tsv")
+        if args.min_group:
+            parser.error("--min-group belongs to --groups-tsv")
+        if args.keep_covered:
+            parser.error("--keep-covered belongs to --groups-tsv")
+    if not args.chains_tsv and not args.groups_tsv:
         for name in ("min_seed", "max_gap"):
             if getattr(args, name) is not None:
-                parser.error(f"--{name.replace('_', '-')} belongs to --chains-tsv")
+                parser.error(f"--{name.replace('_', '-')} belongs to --chains-tsv or --groups-tsv")
         return
-    if args.min_seed is None or args.max_gap is None:
+    if args.groups_tsv:
+        if args.chains_tsv:
+            parser.error("--groups-tsv and --chains-tsv are two lists: ask for one of them per call")
+        if args.min_seed is None or args.max_gap is None or args.max_shift is None:
+            parser.error("--groups-tsv needs --min-seed, --max-gap and --max-shift")
+        if not 1 <= args.max_shift <= 32:
+            parser.error(f"--max-shift is set to {args.max_shift}. It must be 1 .. 32.")
+        if args.min_group < 0:
+            parser.error(f"--min-group is set to {args.min_group}. It must be at least 0.")
+        if args.min_chain:
+            parser.error("--min-chain goes with --chains-tsv: a group needs every chain (use --min-group)")
+        if args.keep_multiples:
+            parser.error("--keep-multiples goes with --chains-tsv (use --keep-covered)")
+    elif args.min_seed is None or args.max_gap is None:
         parser.error("--chains-tsv needs --min-seed and --max-gap")
     if args.min_seed < 1:
         parser.error(f"--min-seed is set to {args.min_seed}. It must be at least 1.")
@@ -65,7 +97,7 @@ def check_chain_args(args, parser):
     if args.chain_window < 1:
         parser.error(f"--chain-window is set to {args.chain_window}. It must be at least 1.")
     if args.window is not None or args.tsv:
-        parser.error("--chains-tsv lists repeats; --window and --tsv belong to the profile")
+        parser.error("--chains-tsv and --groups-tsv list repeats; --window and --tsv belong to the profile")
 
 
 def resolve_input(args, parser):
@@ -100,7 +132,7 @@ def resolve_input(args, parser):
         if not args.input_sequence.isalpha():
             parser.error(f"Invalid input: {args.input_sequence}. This should be a FASTA file path or a string of letters.")
         chrom, seq, begin, end = "sequence", args.input_sequence, 0, len(args.input_sequence)
-    if args.window is None and not args.chains_tsv and end - begin > MAX_MATRIX_POSITIONS:
+    if args.window is None and not args.chains_tsv and not args.groups_tsv and end - begin > MAX_MATRIX_POSITIONS:
         parser.error(f"The input sequence is too long for the full matrix ({end - begin:,d} bp > {MAX_MATRIX_POSITIONS:,d}). "
                      f"Use --window W (a multiple of 64) to plot the periodicity profile instead.")
     return chrom, seq, begin, end
@@ -142,12 +174,48 @@ def list_chains(args, chrom, seq, begin, end, context=None):
     print(f"Wrote {args.chains_tsv}: {len(rows)} repeats")
 
 
+def group_lines(chrom, begin, seq, rows):
+    """The --groups-tsv lines of the rows of prf_native.tandem_groups, whose positions are relative to begin."""
+    for start, stop, period, copies, identity, indel, chains, seeds in rows.tolist():
+        yield (f"{chrom}\t{begin + start}\t{begin + stop}\t{period}\t{copies:.3f}\t{identity:.4f}\t{indel}\t{chains}\t{seeds}\t"
+               f"{seq[begin + start:begin + start + period].upper()}\n")
+
+
+def list_groups(args, chrom, seq, begin, end, context=None):
+    """--groups-tsv: the interval in windows of --chain-window start positions; per window the chains (min_len 0) and the links,
+    which add up over the windows; then the join, the filters and one line per group."""
+    import numpy as np
+    import prf_native
+    ctx = context if context is not None else prf_native.default_context()
+    genome = ctx.load([seq.encode("ascii", "replace")], 64)
+    chains, links = [], []
+    try:
+        for at in range(0, end - begin, args.chain_window):
+            window = (at, min(at + args.chain_window, end - begin))
+            chains.append(genome.period_chains(0, begin, end, args.min_motif_size, args.max_motif_size, args.min_seed, args.max_gap, 0,
+                                               args.n_matches, window))
+            links.append(genome.period_links(0, begin, end, args.min_motif_size, args.max_motif_size, args.min_seed, args.max_gap,
+                                             args.max_shift, args.n_matches, window))
+    finally:
+        genome.free()
+    chains = np.concatenate(chains) if chains else np.zeros(0, dtype=prf_native.PCHAIN_DTYPE)
+    links = np.concatenate(links) if links else np.zeros(0, dtype=prf_native.PLINK_DTYPE)
+    groups = prf_native.join_period_chains(chains, links)
+    rows = prf_native.tandem_groups(groups, drop_covered=not args.keep_covered)
+    rows = rows[(rows["end"] - rows["start"] >= args.min_group) & (rows["identity"] >= args.min_identity)]
+    with open(args.groups_tsv, "wt") as out:
+        out.writelines(group_lines(chrom, begin, seq, rows))
+    print(f"Wrote {args.groups_tsv}: {len(rows)} repeats")
+
+
 def main(argv=None, context=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     chrom, seq, begin, end = resolve_input(args, parser)
     if args.chains_tsv:
         return list_chains(args, chrom, seq, begin, end, context)
+    if args.groups_tsv:
+        return list_groups(args, chrom, seq, begin, end, context)
     from utils.plot_utils import get_period_matrix, plot_periodicity_matrix
     if args.window is None:
         matrix = get_period_matrix(args.min_motif_size, args.max_motif_size, seq[begin:end])

@@ -157,6 +157,18 @@ PCHAIN_DTYPE = [("start", "<u8"), ("len", "<u8"), ("matches", "<u8"), ("k", "<u4
 PCHAIN_MAX_ROWS = 1 << 24            # PRF_PCHAIN_MAX_ROWS
 PCHAIN_LONG_ROWS = 1 << 20           # PRF_PCHAIN_LONG_ROWS
 PCHAIN_DEFAULT_CAPACITY = 1 << 16    # rows the first of the binding's two calls has room for
+# the entry points of the list of junctions between those chains across neighbouring period lines (include/prf_periodlink.h,
+# which prf.h includes)
+PERIODLINK_EXPORTS = ["prf_period_links", "prf_period_links_ex", "prf_period_links_seq"]
+PLINK_DTYPE = [("start", "<u8"), ("from_end", "<u8"), ("k", "<u4"), ("shift", "<i4"), ("gap", "<u4"), ("overlap", "<u4")]   # prf_plink, 32 bytes
+PLINK_DEFAULT_CAPACITY = 1 << 16     # rows the first of the binding's two calls has room for
+# one row of join_period_chains per group of period chains joined by links
+PGROUP_DTYPE = [("start", "<u8"), ("end", "<u8"), ("span_a", "<u8"), ("span_b", "<u8"), ("matches", "<u8"), ("gap_cells", "<u8"),
+                ("k_first", "<u4"), ("k_min", "<u4"), ("k_max", "<u4"), ("period", "<u4"), ("chains", "<u4"), ("seeds", "<u4"),
+                ("indel", "<u4"), ("net_shift", "<i4"), ("open", "?")]
+# one row of tandem_groups per gapped repeat
+TANDEM_GROUP_DTYPE = [("start", "<u8"), ("end", "<u8"), ("period", "<u4"), ("copies", "<f8"), ("identity", "<f8"), ("indel", "<u4"),
+                      ("chains", "<u4"), ("seeds", "<u4")]
 # one row of tandem_rows per repeat
 TANDEM_DTYPE = [("start", "<u8"), ("end", "<u8"), ("k", "<u4"), ("copies", "<f8"), ("identity", "<f8"), ("matches", "<u8"),
                 ("seeds", "<u4")]
@@ -289,6 +301,10 @@ def load_library():
         lib.prf_period_chains.argtypes = [vp, vp, ctypes.c_uint32] + pchains_tail
         lib.prf_period_chains_ex.argtypes = [vp, vp, ctypes.c_uint32] + pchains_tail + [ctypes.c_uint64]
         lib.prf_period_chains_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + pchains_tail
+        plinks_tail = pchains_tail[:9] + [ctypes.c_uint32] + pchains_tail[10:]     # ... max_gap, max_shift, dst, capacity, n_links, stats
+        lib.prf_period_links.argtypes = [vp, vp, ctypes.c_uint32] + plinks_tail
+        lib.prf_period_links_ex.argtypes = [vp, vp, ctypes.c_uint32] + plinks_tail + [ctypes.c_uint64]
+        lib.prf_period_links_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + plinks_tail
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
         lib.prf_measure_hbm_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -644,6 +660,126 @@ def _period_chains(ctx, target, begin, end, kmin, kmax, min_seed, max_gap, min_l
     return (chains, stats) if with_stats else chains
 
 
+def _period_links(ctx, target, begin, end, kmin, kmax, min_seed, max_gap, max_shift, n_matches, positions, with_stats, launch_cells):
+    """The one path of the period_links calls, as _period_chains: once with PLINK_DEFAULT_CAPACITY rows of room and once more with
+    the exact number if there were more."""
+    import numpy as np
+    if isinstance(kmin, bool) or isinstance(kmax, bool) or not 1 <= operator.index(kmin) <= operator.index(kmax) <= 0xFFFFFFFF:
+        raise ValueError(f"periods {kmin} .. {kmax}: an empty range")
+    if isinstance(min_seed, bool) or operator.index(min_seed) < 1:
+        raise ValueError(f"min_seed is set to {min_seed}. It must be at least 1.")
+    if isinstance(max_gap, bool) or not 0 <= operator.index(max_gap) <= DOTCHAIN_MAX_GAP:
+        raise ValueError(f"max_gap is set to {max_gap}. It must be 0 .. {DOTCHAIN_MAX_GAP}.")
+    if isinstance(max_shift, bool) or not 1 <= operator.index(max_shift) <= DOTLINK_MAX_SHIFT:
+        raise ValueError(f"max_shift is set to {max_shift}. It must be 1 .. {DOTLINK_MAX_SHIFT}.")
+    lo, hi = (0, None) if positions is None else positions
+    if lo < 0 or (hi is not None and lo > hi):
+        raise ValueError(f"positions {lo} .. {hi}: an empty range is given as lo == hi")
+    where, _n, c_end, keep = _matrix_range(target, begin, end)
+    args = where + (begin, c_end, lo, END_OF_CONTIG if hi is None else hi, kmin, kmax, 1 if n_matches else 0, min_seed, max_gap, max_shift)
+    if keep is not None:
+        fn, head, tail = ctx.lib.prf_period_links_seq, (ctx._h,), ()
+    else:
+        fn, head, tail = ctx.lib.prf_period_links_ex, (ctx._h, target[0]._h), (launch_cells,)
+    capacity = PLINK_DEFAULT_CAPACITY
+    while True:
+        out = np.zeros(max(1, capacity), dtype=PLINK_DTYPE)
+        n, stats = ctypes.c_uint64(0), ScanStats()
+        _check(ctx.lib, fn(*head, *args, out.ctypes.data_as(ctypes.c_void_p), capacity, ctypes.byref(n), ctypes.byref(stats), *tail))
+        if n.value <= capacity:
+            break
+        if n.value > PCHAIN_MAX_ROWS:
+            raise PrfError(PRF_EUNSUPPORTED, f"{n.value} links are more than one call returns ({PCHAIN_MAX_ROWS}): ask for a larger "
+                                             "min_seed, fewer periods or fewer positions")
+        capacity = n.value
+    links = out[:n.value].copy()
+    return (links, stats) if with_stats else links
+
+
+def join_period_chains(chains, links):
+    """The GAPPED tandem repeats of a window: the chains of period_chains (fetched at min_len = 0) joined along the links of
+    period_links of the same window, range of k, min_seed and max_gap; join_chains' sibling.  Every chain has at most one link in
+    and one out, so the links form paths; one row of PGROUP_DTYPE per path (a chain without links is a path of one), in the order
+    of the paths' first chains: start: the first chain's; end: the last chain's start + len + k (the positions the repeat
+    covers are [start, end)); k_first, k_min, k_max: the first chain's line, the smallest and the largest of the path; period:
+    the k of the chain with the most matches (ties: the smaller k); chains, seeds; matches: the chains' matches minus the
+    overlaps of the links inside the group; indel: the sum of |shift| -- an indel of d bases inside a repeat of period >=
+    min_seed counts 2 d, out to the detour line and back, one of d bases at the repeat's end or between two different periods
+    counts d; net_shift: the sum of the shifts (k_last - k_first); gap_cells: the sum of the links' gaps; span_a: the last
+    chain's last cell - start + 1; span_b = span_a + k_last - k_first; open: a link into the group's first chain names a
+    predecessor that is not in `chains` (it lies on a line outside the range of k or in front of the window)."""
+    import numpy as np
+    n = len(chains)
+    start, length, line = (chains[f].astype(np.int64) for f in ("start", "len", "k"))
+    first = {key: at for at, key in enumerate(zip(start.tolist(), line.tolist()))}
+    last_cell = start + length - 1
+    last = {key: at for at, key in enumerate(zip(last_cell.tolist(), line.tolist()))}
+    nxt, link_of, has_in, is_open = [-1] * n, [-1] * n, [False] * n, [False] * n
+    for at, (t_s, t_e, k, s) in enumerate(zip(*(links[f].tolist() for f in ("start", "from_end", "k", "shift")))):
+        y = first.get((t_s, k))
+        if y is None:
+            raise ValueError(f"the link into (start {t_s}, k {k}) names a successor that is not in the list of chains: "
+                             "join_period_chains needs the chains of the same window, range of k, min_seed and max_gap, fetched at min_len = 0")
+        x = last.get((t_e, k - s))
+        if x is None:
+            is_open[y] = True
+        else:
+            nxt[x], link_of[x], has_in[y] = y, at, True
+    out = np.zeros(n - sum(has_in), dtype=PGROUP_DTYPE)
+    matches, seeds, ks = chains["matches"].tolist(), chains["seeds"].tolist(), line.tolist()
+    shift, gap, overlap = (links[f].tolist() for f in ("shift", "gap", "overlap"))
+    at = 0
+    for head in range(n):
+        if has_in[head]:
+            continue
+        g, cur = out[at], head
+        total = n_seeds = n_chains = indel = net = gap_cells = 0
+        k_min = k_max = ks[cur]
+        best = (-1, 0)                                          # (matches, -k) of the chain that names the period
+        while True:
+            total, n_seeds, n_chains = total + matches[cur], n_seeds + seeds[cur], n_chains + 1
+            k_min, k_max, best = min(k_min, ks[cur]), max(k_max, ks[cur]), max(best, (matches[cur], -ks[cur]))
+            if nxt[cur] < 0:
+                break
+            via = link_of[cur]
+            total, indel, net, gap_cells = total - overlap[via], indel + abs(shift[via]), net + shift[via], gap_cells + gap[via]
+            cur = nxt[cur]
+        g["start"], g["end"], g["open"] = start[head], start[cur] + length[cur] + ks[cur], is_open[head]
+        g["k_first"], g["k_min"], g["k_max"], g["period"] = ks[head], k_min, k_max, -best[1]
+        g["span_a"] = last_cell[cur] - start[head] + 1
+        g["span_b"] = int(g["span_a"]) + ks[cur] - ks[head]
+        g["matches"], g["seeds"], g["chains"], g["indel"], g["net_shift"], g["gap_cells"] = total, n_seeds, n_chains, indel, net, gap_cells
+        at += 1
+    return out
+
+
+def tandem_groups(groups, drop_covered=True):
+    """The repeats of a list of join_period_chains, one row of TANDEM_GROUP_DTYPE each, in the list's order: start, end, period,
+    copies = (end - start) / period, identity = matches / max(span_a, span_b), indel, chains, seeds.  A repeat of period 3 is
+    also periodic at 6, 9, ... and, with an indel, at neighbouring lines: drop_covered removes a group iff another group of the
+    list with a strictly smaller period covers its [start, end).  Host numpy."""
+    import numpy as np
+    out = np.zeros(len(groups), dtype=TANDEM_GROUP_DTYPE)
+    for f in ("start", "end", "period", "indel", "chains", "seeds"):
+        out[f] = groups[f]
+    out["copies"] = (groups["end"] - groups["start"]).astype(np.float64) / np.maximum(groups["period"], 1).astype(np.float64)
+    out["identity"] = groups["matches"].astype(np.float64) / np.maximum(np.maximum(groups["span_a"], groups["span_b"]), 1).astype(np.float64)
+    if not drop_covered or len(out) < 2:
+        return out
+    # by start, longest first, smallest period first: a group can only be covered by a group in front of it in this order (or by
+    # one with the same interval, which has a smaller period and sorts in front).  Of the groups in front, per period, the
+    # largest end is kept; a prefix minimum over the periods answers "does a smaller period reach behind my end".
+    order = np.lexsort((out["period"], -out["end"].astype(np.int64), out["start"].astype(np.int64)))
+    keep = np.ones(len(out), dtype=bool)
+    reach = {}                                                  # period -> the largest end of the groups in front
+    for at, p, b in zip(order.tolist(), out["period"][order].tolist(), out["end"][order].tolist()):
+        if any(e >= b for q, e in reach.items() if q < p):
+            keep[at] = False
+        if reach.get(p, 0) < b:
+            reach[p] = b
+    return out[keep]
+
+
 def tandem_rows(chains, drop_multiples=True):
     """The repeats of a list of period_chains, one row of TANDEM_DTYPE each, in the list's order: start, end = start + len + k (the
     positions the repeat covers), k, copies = (len + k) / k, identity = matches / len, matches, seeds.  A repeat of period 3 is
@@ -862,6 +998,18 @@ class Genome:
         return _period_chains(self.ctx, (self, contig), begin, end, kmin, kmax, min_seed, max_gap, min_len, n_matches, positions,
                               with_stats, launch_cells)
 
+    def period_links(self, contig, begin, end, kmin, kmax, min_seed, max_gap, max_shift, n_matches=False, positions=None,
+                     with_stats=False, launch_cells=0):
+        """The INDEL JUNCTIONS between the chains of period_chains at the same min_seed and max_gap (prf_period_links): chain X
+        ends on line k - shift, chain Y starts on line k, 1 .. max_shift lines away, at most max_gap cells behind (or up to
+        min(min_seed - 1, 16) cells in front), and each is the other's best such neighbour.  A numpy structured array with the
+        fields start, k (the key of Y's row in the list of chains), from_end (X's last cell), shift, gap and overlap, sorted by
+        (start, k): the links whose Y starts in positions = (pos0, pos1) (None: all) on a line kmin .. kmax.  Links are judged
+        against every line 1 .. n - 1 of the range: the lists of a partition in positions or in k add up, and X may lie on a line
+        outside kmin .. kmax.  join_period_chains() folds the two lists into gapped tandem repeats."""
+        return _period_links(self.ctx, (self, contig), begin, end, kmin, kmax, min_seed, max_gap, max_shift, n_matches, positions,
+                             with_stats, launch_cells)
+
     @property
     def positions(self):
         return self.ctx.lib.prf_genome_positions(self._h)
@@ -1074,6 +1222,11 @@ class Context:
                       with_stats=False):
         """Genome.period_chains for one sequence (str or bytes) in one call: load, list, free (prf_period_chains_seq)."""
         return _period_chains(self, seq, begin, end, kmin, kmax, min_seed, max_gap, min_len, n_matches, positions, with_stats, 0)
+
+    def period_links(self, seq, kmin, kmax, min_seed, max_gap, max_shift, n_matches=False, begin=0, end=None, positions=None,
+                     with_stats=False):
+        """Genome.period_links for one sequence (str or bytes) in one call: load, list, free (prf_period_links_seq)."""
+        return _period_links(self, seq, begin, end, kmin, kmax, min_seed, max_gap, max_shift, n_matches, positions, with_stats, 0)
 
     def period_counts(self, seq, kmin, kmax, window, begin=0, end=None, with_stats=False):
         """Genome.period_counts for one sequence (str or bytes) in one call: load, count, free (prf_period_counts_seq)."""

@@ -357,6 +357,10 @@ int prf_measure_hbm_read(prf_ctx *ctx, uint64_t bytes, int iters, double *gbps);
  * additions to ABI version 4, declared in prf_periodchain.h, which this header includes here; prf_scan_stats.path = 10 is theirs. */
 #include "prf_periodchain.h"
 
+/* ---- the indel junctions between those chains across neighbouring period lines: three more entry points, additions
+ * to ABI version 4, declared in prf_periodlink.h, which this header includes here; prf_scan_stats.path = 11 is theirs. */
+#include "prf_periodlink.h"
+
 #ifdef __cplusplus
 }
 #endif
