@@ -1,180 +1,76 @@
-// dotlink_host.cpp -- the host path of the list of junctions between the chains of the dot plot of two ranges (prf_dotpair_links,
-// its _ex and one-shot forms; kernels: dotruns.hip for the seeds, dotlink.hip for the heads and the join).  Modelled on
-// dotchain_host.cpp, whose order of refusals it keeps and whose seeds it shares (dotseeds_host.h).  One call = one window of
-// start cells of the successors:
-//   1. the seeds of the window, as dotchain_host.cpp finds them; they stay on the device.
+// dotlink_host.cpp -- the list of junctions between the chains of the dot plot of two ranges (prf_dotpair_links, its _ex and
+// one-shot forms; kernels: dotruns.hip for the seeds, dotlink.hip for the heads and the join) as a request on the frame
+// of list_host.h.  One call = one window of start cells of the successors:
+//   1. the seeds of the window at min_len = min_seed (dotseeds_host.h); they stay on the device.
 //   2. the heads kernel, one thread per seed: the indices of the seeds that start a chain.
 //   3. the join kernel, one wave per head: at most one link each.
-// The rows are copied and sorted here.  No selection is read, no row sink written, the last scan's rows stay.
-#include <algorithm>
-#include <vector>
-
 #include "dotseeds_host.h"
 
 namespace {
 
-struct links_request {
+struct links_request : pair_window, list_output<prf_dotlink, prf_dotlink_dev> {
     static constexpr u32 path = 9;
-    u64 begin, end;     // A's range
-    u32 b_contig;
-    u64 b_begin, b_end;
-    u32 strand;
-    u64 row0, row1, col0, col1;
-    u32 directions;
     u64 min_seed;
     u32 max_gap, max_shift;
-    prf_dotlink *dst;
-    u64 capacity;
-    uint64_t *n_links;
-    u64 launch_cells;   // 0: PRF_DOT_LAUNCH_CELLS
-    using room = seeds_room;
 
     int check(const char *name) const {
-        if (begin > end) return fail(PRF_EINVAL, "%s: a_begin %llu is behind a_end %llu", name, (unsigned long long)begin, (unsigned long long)end);
-        if (b_begin > b_end)
-            return fail(PRF_EINVAL, "%s: b_begin %llu is behind b_end %llu", name, (unsigned long long)b_begin, (unsigned long long)b_end);
-        if (row0 > row1) return fail(PRF_EINVAL, "%s: row0 %llu is behind row1 %llu", name, (unsigned long long)row0, (unsigned long long)row1);
-        if (col0 > col1) return fail(PRF_EINVAL, "%s: col0 %llu is behind col1 %llu", name, (unsigned long long)col0, (unsigned long long)col1);
-        if (strand > 1) return fail(PRF_EINVAL, "%s: strand is %u. It must be 0 (plus) or 1 (minus).", name, strand);
-        if (!directions || directions > 3)
-            return fail(PRF_EINVAL, "%s: directions is %u. It must be 1 (main), 2 (anti) or 3 (both).", name, directions);
-        if (!min_seed) return fail(PRF_EINVAL, "%s: min_seed is 0. It must be at least 1.", name);
-        if (max_gap > PRF_DOTCHAIN_MAX_GAP)
-            return fail(PRF_EUNSUPPORTED, "%s: a max_gap of %u cells is above %u (PRF_DOTCHAIN_MAX_GAP)", name, max_gap, PRF_DOTCHAIN_MAX_GAP);
-        if (!max_shift) return fail(PRF_EINVAL, "%s: max_shift is 0. It must be at least 1: chains of one line are joined by max_gap.", name);
-        if (max_shift > PRF_DOTLINK_MAX_SHIFT)
-            return fail(PRF_EUNSUPPORTED, "%s: a max_shift of %u lines is above %u (PRF_DOTLINK_MAX_SHIFT)", name, max_shift, PRF_DOTLINK_MAX_SHIFT);
-        if (capacity > PRF_DOTCHAIN_MAX_ROWS)
-            return fail(PRF_EUNSUPPORTED, "%s: a capacity of %llu rows is above %llu (PRF_DOTCHAIN_MAX_ROWS)", name,
-                        (unsigned long long)capacity, (unsigned long long)PRF_DOTCHAIN_MAX_ROWS);
-        if (!n_links) return fail(PRF_EINVAL, "%s: NULL n_links", name);
-        if (!dst && capacity) return fail(PRF_EINVAL, "%s: NULL destination with a capacity of %llu rows", name, (unsigned long long)capacity);
-        return PRF_OK;
+        int rc = check_window(name);
+        if (!rc) rc = list_check_seed_gap(name, min_seed, max_gap);
+        if (!rc) rc = list_check_shift(name, max_shift);
+        if (!rc) rc = list_check_output(name, dst, capacity, n_out, "n_links", PRF_DOTCHAIN_MAX_ROWS, "PRF_DOTCHAIN_MAX_ROWS");
+        return rc;
     }
 
-    int check_room(const char *name, u64 a_len, room *o) const {
-        return seeds_check_room(name, begin, end, b_begin, b_end, row0, row1, col0, col1, a_len, o);
-    }
-};
-
-int links_run(const char *name, prf_ctx *c, const prf_genome *g, u32 contig, const links_request &r, prf_scan_stats *stats) {
-    if (!c) return fail(PRF_EINVAL, "%s: NULL context", name);
-    prf_contig_view v, vb;
-    int rc = prf_genome_contig_view(g, contig, &v);
-    if (rc) return rc;
-    if (v.ctx != c) return fail(PRF_EINVAL, "%s: the genome belongs to another context", name);
-    if ((rc = prf_genome_contig_view(g, r.b_contig, &vb))) return rc;
-    links_request::room o{};
-    o.b_base = vb.base;
-    o.b_len = vb.len;
-    if ((rc = r.check_room(name, v.len, &o))) return rc;
-    if ((rc = refuse_in_flight(c, name))) return rc;
-    HIPCHK(hipSetDevice(c->dev));
-    float ms = 0, ms_seeds = 0;
-    u32 launches = 0;
-    u64 n_links = 0, n_seeds = 0, n_heads = 0;
-    if (o.row1 > o.row0 && o.col1 > o.col0) {
+    // n_candidates: the chain heads of the window; the phases: the seed kernels, the link kernels
+    int body(const char *name, prf_ctx *c, const prf_contig_view &v, const room &o, dev_array<prf_dotlink_dev> &d_out, list_result &res) const {
         dev_array<prf_dotrun_dev> d_seeds, d_long;
         dev_array<u64> d_cnt;
-        const prf_dotruns_args a = seeds_args(v, o, r.begin, r.b_begin, r.strand, r.directions, r.min_seed);
+        const prf_dotruns_args a = seeds_args(v, o, *this, min_seed);
+        u64 n_seeds = 0;
+        int rc;
         if ((rc = d_long.alloc(a.long_cap)) || (rc = d_cnt.alloc(PRF_DR_N + PRF_DL_N))) return rc;
         // ---- 1. the seeds
-        if ((rc = all_seeds(name, c, a, r.launch_cells, o, d_seeds, d_long, d_cnt.p, &n_seeds, &ms, &launches))) return rc;
-        ms_seeds = ms;
-        if (n_seeds) {
-            // ---- 2. the heads: every seed is at most one entry
-            dev_array<u32> d_heads;
-            dev_array<prf_dotlink_dev> d_out;
-            prf_dotlink_args k{};
-            k.seed_rows = d_seeds.p;
-            k.n_seeds = n_seeds;
-            k.min_seed = r.min_seed;
-            k.max_gap = r.max_gap;
-            k.max_shift = r.max_shift;
-            k.capacity = r.capacity;
-            k.counters = d_cnt.p + PRF_DR_N;
-            if ((rc = d_heads.alloc(n_seeds)) || (rc = d_out.alloc(k.capacity))) return rc;
-            k.heads = d_heads.p;
-            k.dst = d_out.p;
-            float part = 0;
-            HIPCHK(hipMemsetAsync(k.counters, 0, PRF_DL_N * sizeof(u64), c->stream));
-            HIPCHK(hipEventRecord(c->ev[0], c->stream));
+        if ((rc = all_seeds(name, c, a, launch_cells, o, d_seeds, d_long, d_cnt.p, &n_seeds, &res.ms1, &res.launches))) return rc;
+        if (!n_seeds) return PRF_OK;
+        // ---- 2. the heads: every seed is at most one entry
+        dev_array<u32> d_heads;
+        prf_dotlink_args k{};
+        k.seed_rows = d_seeds.p;
+        k.n_seeds = n_seeds;
+        k.min_seed = min_seed;
+        k.max_gap = max_gap;
+        k.max_shift = max_shift;
+        k.capacity = capacity;
+        k.counters = d_cnt.p + PRF_DR_N;
+        if ((rc = d_heads.alloc(n_seeds)) || (rc = d_out.alloc(k.capacity))) return rc;
+        k.heads = d_heads.p;
+        k.dst = d_out.p;
+        u64 cnt[PRF_DL_N] = {0, 0};
+        HIPCHK(hipMemsetAsync(k.counters, 0, PRF_DL_N * sizeof(u64), c->stream));
+        rc = timed_step(c, [&]() -> int {
             HIPCHK(prf_launch_dotlink_heads(c->stream, a, k));
-            ++launches;
-            HIPCHK(hipEventRecord(c->ev[1], c->stream));
-            u64 cnt[PRF_DL_N] = {0, 0};
-            HIPCHK(hipMemcpyAsync(cnt, k.counters, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            HIPCHK(hipEventElapsedTime(&part, c->ev[0], c->ev[1]));
-            ms += part;
-            n_heads = cnt[PRF_DL_HEADS];
-            if (n_heads > n_seeds)
-                return fail(PRF_EHIP, "%s: %llu chain heads among %llu seeds", name, (unsigned long long)n_heads, (unsigned long long)n_seeds);
-            // ---- 3. the join: every head is at most one link
-            if (n_heads) {
-                HIPCHK(hipEventRecord(c->ev[0], c->stream));
-                HIPCHK(prf_launch_dotlink_join(c->stream, a, k, n_heads));
-                ++launches;
-                HIPCHK(hipEventRecord(c->ev[1], c->stream));
-                HIPCHK(hipMemcpyAsync(cnt, k.counters, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipStreamSynchronize(c->stream));
-                HIPCHK(hipEventElapsedTime(&part, c->ev[0], c->ev[1]));
-                ms += part;
-            }
-            n_links = cnt[PRF_DL_LINKS];
-            if (n_links > n_heads)
-                return fail(PRF_EHIP, "%s: %llu links into %llu chain heads", name, (unsigned long long)n_links, (unsigned long long)n_heads);
-            if (n_links && n_links <= r.capacity) {
-                std::vector<prf_dotlink> got(n_links);
-                static_assert(sizeof(prf_dotlink) == sizeof(prf_dotlink_dev), "one layout");
-                HIPCHK(hipMemcpy(got.data(), d_out.p, n_links * sizeof(prf_dotlink), hipMemcpyDeviceToHost));
-                std::sort(got.begin(), got.end(), [](const prf_dotlink &x, const prf_dotlink &y) {
-                    return x.row != y.row ? x.row < y.row : x.col != y.col ? x.col < y.col : x.dir < y.dir;
-                });
-                memcpy(r.dst, got.data(), n_links * sizeof(prf_dotlink));
-            }
-        }
-    }
-    *r.n_links = n_links;
-    lane_stats(stats, links_request::path, ms, o.na + o.nb, (o.na + o.nb + 3) / 4, launches);
-    if (stats) {
-        stats->n_hits = n_links;
-        stats->n_candidates = n_heads;       // the chain heads of the window; the time of the seed kernels and of the link kernels
-        stats->phase1_ms = ms_seeds;
-        stats->phase2_ms = ms - ms_seeds;
-    }
-    return PRF_OK;
-}
-
-int links_on_genome(const char *name, prf_ctx *c, const prf_genome *g, u32 contig, const links_request &r, prf_scan_stats *stats) {
-    return guarded(name, [&] {
-        const int rc = r.check(name);
-        return rc ? rc : links_run(name, c, g, contig, r, stats);
-    });
-}
-
-// two sequences become contigs 0 (A) and 1 (B) of a genome that lives for the call, as chains_one_shot (dotchain_host.cpp) loads
-// them.  Everything that can be refused from the arguments and the bytes is refused before the context is looked at.
-int links_one_shot(const char *name, prf_ctx *c, const prf_contig *seq_a, const prf_contig *seq_b, const links_request &r,
-                   prf_scan_stats *stats) {
-    return guarded(name, [&] {
-        int rc = r.check(name);
+            ++res.launches;
+            return PRF_OK;
+        }, cnt, k.counters, PRF_DL_N, &res.ms2);
         if (rc) return rc;
-        for (const prf_contig *seq : {seq_a, seq_b})
-            if (!seq || (seq->len && !seq->ascii)) return fail(PRF_EINVAL, "%s: NULL sequence", name);
-        links_request::room o{};
-        o.b_len = seq_b->len;
-        if ((rc = r.check_room(name, seq_a->len, &o))) return rc;
-        if ((rc = matrix_check_letters(name, seq_a)) || (rc = matrix_check_letters(name, seq_b))) return rc;
-        if (!c) return fail(PRF_EINVAL, "%s: NULL context", name);
-        const prf_contig both[2] = {*seq_a, *seq_b};
-        prf_genome *g = nullptr;
-        if ((rc = prf_genome_load(c, both, 2, 64, &g))) return rc;
-        rc = links_run(name, c, g, 0, r, stats);
-        prf_genome_free(g);
-        return rc;
-    });
-}
+        const u64 n_heads = res.n_candidates = cnt[PRF_DL_HEADS];
+        if (n_heads > n_seeds)
+            return fail(PRF_EHIP, "%s: %llu chain heads among %llu seeds", name, (unsigned long long)n_heads, (unsigned long long)n_seeds);
+        // ---- 3. the join: every head is at most one link
+        if (n_heads) {
+            rc = timed_step(c, [&]() -> int {
+                HIPCHK(prf_launch_dotlink_join(c->stream, a, k, n_heads));
+                ++res.launches;
+                return PRF_OK;
+            }, cnt, k.counters, PRF_DL_N, &res.ms2);
+            if (rc) return rc;
+        }
+        res.n = cnt[PRF_DL_LINKS];
+        if (res.n > n_heads)
+            return fail(PRF_EHIP, "%s: %llu links into %llu chain heads", name, (unsigned long long)res.n, (unsigned long long)n_heads);
+        return PRF_OK;
+    }
+};
 
 }  // namespace
 
@@ -184,10 +80,10 @@ int prf_dotpair_links_ex(prf_ctx *c, const prf_genome *g, uint32_t a_contig, uin
                          uint64_t b_begin, uint64_t b_end, uint32_t strand, uint64_t row0, uint64_t row1, uint64_t col0, uint64_t col1,
                          uint32_t directions, uint64_t min_seed, uint32_t max_gap, uint32_t max_shift, prf_dotlink *dst,
                          uint64_t capacity, uint64_t *n_links, prf_scan_stats *stats, uint64_t launch_cells) {
-    return links_on_genome("prf_dotpair_links", c, g, a_contig,
-                           links_request{a_begin, a_end, b_contig, b_begin, b_end, strand, row0, row1, col0, col1, directions, min_seed,
-                                         max_gap, max_shift, dst, capacity, n_links, launch_cells},
-                           stats);
+    return list_on_genome("prf_dotpair_links", c, g, a_contig,
+                          links_request{{a_begin, a_end, b_contig, b_begin, b_end, strand, row0, row1, col0, col1, directions},
+                                        {dst, capacity, n_links, launch_cells}, min_seed, max_gap, max_shift},
+                          stats);
 }
 
 int prf_dotpair_links(prf_ctx *c, const prf_genome *g, uint32_t a_contig, uint64_t a_begin, uint64_t a_end, uint32_t b_contig,
@@ -202,10 +98,10 @@ int prf_dotpair_links_seq(prf_ctx *c, const prf_contig *seq_a, uint64_t a_begin,
                           uint64_t b_begin, uint64_t b_end, uint32_t strand, uint64_t row0, uint64_t row1, uint64_t col0,
                           uint64_t col1, uint32_t directions, uint64_t min_seed, uint32_t max_gap, uint32_t max_shift, prf_dotlink *dst,
                           uint64_t capacity, uint64_t *n_links, prf_scan_stats *stats) {
-    return links_one_shot("prf_dotpair_links_seq", c, seq_a, seq_b,
-                          links_request{a_begin, a_end, 1, b_begin, b_end, strand, row0, row1, col0, col1, directions, min_seed, max_gap,
-                                        max_shift, dst, capacity, n_links, 0},
-                          stats);
+    return list_one_shot("prf_dotpair_links_seq", c, {seq_a, seq_b},
+                         links_request{{a_begin, a_end, 1, b_begin, b_end, strand, row0, row1, col0, col1, directions},
+                                       {dst, capacity, n_links, 0}, min_seed, max_gap, max_shift},
+                         stats);
 }
 
 }  // extern "C"

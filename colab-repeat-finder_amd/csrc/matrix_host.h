@@ -1,6 +1,6 @@
 // matrix_host.h -- the host path that the matrix products share (periodicity_host.cpp, dotplot_host.cpp, dotpair_host.cpp;
-// dotruns_host.cpp and periodchain_host.cpp include it for the helpers and run their own output, a list with a count; nobody else
-// includes it).
+// list_host.h, the frame of the products whose output is a list with a count, includes it for matrix_clip and
+// matrix_check_letters; nobody else includes it).
 //
 // One call = one range of one contig of a resident genome (a product of two ranges names the second one in its request and
 // resolves it in check_view): judge the arguments (before the context or the genome is looked at),

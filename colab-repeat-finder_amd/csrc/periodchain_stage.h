@@ -1,12 +1,11 @@
-// periodchain_stage.h -- what the two host paths that work on the CHAINS of a window of period lines share (periodchain_host.cpp,
-// DESIGN 16; periodlink_host.cpp; nobody else includes it): the clipped range and window, the arguments of the kernels
-// of periodchain.hip, and the stage that runs them and leaves the rows on the device.  Moved here unchanged from
-// periodchain_host.cpp:
+// periodchain_stage.h -- the stage of the list products of the period lines of a range (periodchain_host.cpp, DESIGN 16;
+// periodlink_host.cpp; nobody else includes it): the window of a request and its refusals, the clipped range, the
+// arguments of the kernels of periodchain.hip, and the stage that runs them and leaves the rows on the device:
 //   1. the find kernel over the words of the window, cut into launches of at most launch_cells cells: rows, or entries of the
 //      long list;
 //   2. the long kernel for the first runs and chains the find kernel left, one wave each.
 #pragma once
-#include "matrix_host.h"
+#include "list_host.h"
 
 namespace {
 
@@ -15,34 +14,58 @@ struct pchain_room {
     u64 pos0, pos1;     // the clipped window
 };
 
-int pchain_check_room(const char *name, u64 begin, u64 end, u64 pos0, u64 pos1, u32 kmin, u32 kmax, u64 seq_len, pchain_room *o) {
-    const int rc = matrix_clip(name, begin, end, seq_len, &o->n);
-    if (rc) return rc;
-    o->pos1 = pos1 < o->n ? pos1 : o->n;
-    o->pos0 = pos0 < o->pos1 ? pos0 : o->pos1;
-    const u64 starts = o->pos1 - o->pos0, nk = (u64)kmax - kmin + 1;
-    if (starts && nk > PRF_DOT_MAX_CELLS / starts)
-        return fail(PRF_EUNSUPPORTED, "%s: a window of %llu positions x %llu lines is above the limit of 2^42 cells per call (PRF_DOT_MAX_CELLS)",
-                    name, (unsigned long long)starts, (unsigned long long)nk);
-    return PRF_OK;
-}
+// The window of a request of one range, start positions x a range of k, and what the frame of list_host.h asks of it
+struct period_window {
+    static constexpr bool pair = false;
+    using room = pchain_room;
+    u64 begin, end;
+    u64 pos0, pos1;
+    u32 kmin, kmax, n_matches;
 
-// a window with starts and lines: a line k >= n is empty
-bool pchain_any(const pchain_room &o, u32 kmin) { return o.pos1 > o.pos0 && (u64)kmin < o.n; }
+    int check_window(const char *name) const {
+        if (begin > end) return fail(PRF_EINVAL, "%s: begin %llu is behind end %llu", name, (unsigned long long)begin, (unsigned long long)end);
+        if (pos0 > pos1) return fail(PRF_EINVAL, "%s: pos0 %llu is behind pos1 %llu", name, (unsigned long long)pos0, (unsigned long long)pos1);
+        if (!kmin) return fail(PRF_EINVAL, "%s: kmin is 0. It must be at least 1.", name);
+        if (kmin > kmax) return fail(PRF_EINVAL, "%s: kmin %u is above kmax %u", name, kmin, kmax);
+        if (n_matches > 1) return fail(PRF_EINVAL, "%s: n_matches is %u. It must be 0 (N never matches) or 1 (N == N matches).", name, n_matches);
+        return PRF_OK;
+    }
 
-// the kernels' arguments for such a window; dst, capacity, longs and counters are the stage's
-prf_periodchain_args pchain_args(const prf_contig_view &v, const pchain_room &o, u64 begin, u32 kmin, u32 kmax, u32 n_matches, u64 min_seed,
-                                 u32 max_gap, u64 min_len) {
+    int check_room(const char *name, u64 seq_len, room *o) const {
+        const int rc = matrix_clip(name, begin, end, seq_len, &o->n);
+        if (rc) return rc;
+        o->pos1 = pos1 < o->n ? pos1 : o->n;
+        o->pos0 = pos0 < o->pos1 ? pos0 : o->pos1;
+        const u64 starts = o->pos1 - o->pos0, nk = (u64)kmax - kmin + 1;
+        if (starts && nk > PRF_DOT_MAX_CELLS / starts)
+            return fail(PRF_EUNSUPPORTED, "%s: a window of %llu positions x %llu lines is above the limit of 2^42 cells per call (PRF_DOT_MAX_CELLS)",
+                        name, (unsigned long long)starts, (unsigned long long)nk);
+        return PRF_OK;
+    }
+
+    // a window with starts and lines: a line k >= n is empty
+    bool any(const room &o) const { return o.pos1 > o.pos0 && (u64)kmin < o.n; }
+    u64 positions(const room &o) const { return o.n; }
+
+    template <class Row>
+    static bool less(const Row &x, const Row &y) {
+        return x.start != y.start ? x.start < y.start : x.k < y.k;
+    }
+};
+
+// the kernels' arguments for a window that is not empty; dst, capacity, longs and counters are the stage's
+prf_periodchain_args pchain_args(const prf_contig_view &v, const pchain_room &o, const period_window &w, u64 min_seed, u32 max_gap,
+                                 u64 min_len) {
     prf_periodchain_args a{};
     a.pl = v.planes;
-    a.g_begin = v.base + begin;
+    a.g_begin = v.base + w.begin;
     a.n = o.n;
     a.n_words = (o.n + 63) / 64;
     a.pos0 = o.pos0;
     a.pos1 = o.pos1;
-    a.kmin = kmin;
-    a.kmax = (u64)kmax < o.n ? kmax : (u32)(o.n - 1);
-    a.n_matches = n_matches;
+    a.kmin = w.kmin;
+    a.kmax = (u64)w.kmax < o.n ? w.kmax : (u32)(o.n - 1);
+    a.n_matches = w.n_matches;
     a.max_gap = max_gap;
     a.min_seed = min_seed;
     a.min_len = min_len;
@@ -73,33 +96,26 @@ int pchain_rows(const char *name, prf_ctx *c, prf_periodchain_args a, u64 launch
     if (spans < 1) spans = 1;
     if (spans > (1ull << 30)) spans = 1ull << 30;
     const u64 w_end = (a.pos1 + 63) / 64;
-    float part = 0;
-    HIPCHK(hipEventRecord(c->ev[0], c->stream));
-    for (u64 w = a.pos0 / 64; w < w_end; w += spans * span_words) {
-        a.word0 = w;
-        a.word1 = w_end - w > spans * span_words ? w + spans * span_words : w_end;
-        HIPCHK(prf_launch_periodchain_find(c->stream, a));
-        ++*launches;
-    }
-    HIPCHK(hipEventRecord(c->ev[1], c->stream));
-    HIPCHK(hipMemcpyAsync(cnt, d_cnt.p, PRF_PC_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipEventElapsedTime(&part, c->ev[0], c->ev[1]));
-    *ms += part;
+    rc = timed_step(c, [&]() -> int {
+        for (u64 w = a.pos0 / 64; w < w_end; w += spans * span_words) {
+            a.word0 = w;
+            a.word1 = w_end - w > spans * span_words ? w + spans * span_words : w_end;
+            HIPCHK(prf_launch_periodchain_find(c->stream, a));
+            ++*launches;
+        }
+        return PRF_OK;
+    }, cnt, d_cnt.p, PRF_PC_N, ms);
+    if (rc) return rc;
     if (cnt[PRF_PC_LONG] > a.long_cap)
         return fail(PRF_EUNSUPPORTED, "%s: %llu runs and chains are still going %u cells (PRF_DOTCHAIN_FOLLOW) behind their start, the call keeps room for %llu: ask for a smaller window",
                     name, (unsigned long long)cnt[PRF_PC_LONG], PRF_DOTCHAIN_FOLLOW, (unsigned long long)a.long_cap);
     // ---- 2. what the find kernel left
-    if (cnt[PRF_PC_LONG]) {
-        HIPCHK(hipEventRecord(c->ev[0], c->stream));
-        HIPCHK(prf_launch_periodchain_long(c->stream, a, cnt[PRF_PC_LONG]));
-        ++*launches;
-        HIPCHK(hipEventRecord(c->ev[1], c->stream));
-        HIPCHK(hipMemcpyAsync(cnt, d_cnt.p, PRF_PC_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipEventElapsedTime(&part, c->ev[0], c->ev[1]));
-        *ms_long += part;
-    }
+    if (cnt[PRF_PC_LONG])
+        return timed_step(c, [&]() -> int {
+            HIPCHK(prf_launch_periodchain_long(c->stream, a, cnt[PRF_PC_LONG]));
+            ++*launches;
+            return PRF_OK;
+        }, cnt, d_cnt.p, PRF_PC_N, ms_long);
     return PRF_OK;
 }
 

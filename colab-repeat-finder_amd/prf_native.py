@@ -498,202 +498,120 @@ def _matrix(ctx, target, begin, end, with_stats, period=None, dot=None, versus=N
     return (out, stats) if with_stats else out
 
 
-def _runs(ctx, a_target, a_range, b_target, b_range, strand, directions, min_len, rows, cols, with_stats, launch_cells):
-    """The one path of the dotpair_runs calls: the targets are (genome, contig) pairs of one genome, or two sequences.  Calls once
-    with DOTRUN_DEFAULT_CAPACITY rows of room and once more with the exact number if there were more."""
-    import numpy as np
+def _int_check(name, value, lo, hi=None):
+    """Refuses a value that is no integer (a bool is none) of lo .. hi; hi None: no upper bound."""
+    if isinstance(value, bool) or operator.index(value) < lo or (hi is not None and operator.index(value) > hi):
+        raise ValueError(f"{name} is set to {value}. It must be " + (f"at least {lo}." if hi is None else f"{lo} .. {hi}."))
+
+
+def _list_entry(ctx, name, genome, launch_cells):
+    """(entry point, what it is given in front of the ranges, what behind the stats) of a list product: the one-shot _seq form for
+    sequences (genome None), the _ex form, which takes launch_cells, on a genome."""
+    if genome is None:
+        return getattr(ctx.lib, name + "_seq"), (ctx._h,), ()
+    return getattr(ctx.lib, name + "_ex"), (ctx._h, genome._h), (launch_cells,)
+
+
+def _pair_list_args(ctx, name, a_target, a_range, b_target, b_range, strand, directions, params, rows, cols, launch_cells):
+    """(entry point, head, args, tail, what must stay alive during the call) of a list product of the dot plot of two ranges: the
+    targets are (genome, contig) pairs of one genome, or two sequences.  params: (name, value, lo, hi) of the integers the entry
+    point takes behind `directions`, in its order, checked in that order."""
     if strand not in STRANDS:
         raise ValueError(f"strand is {strand!r}. It must be '+' or '-'.")
     if directions not in DIRECTIONS:
         raise ValueError(f"directions is {directions!r}. It must be 'main', 'anti' or 'both'.")
-    if isinstance(min_len, bool) or operator.index(min_len) < 1:
-        raise ValueError(f"min_len is set to {min_len}. It must be at least 1.")
+    for param in params:
+        _int_check(*param)
     one_shot = not isinstance(a_target, tuple)
     if one_shot == isinstance(b_target, tuple):
         raise ValueError("the two ranges must both be sequences or both lie in a genome")
     if not one_shot and b_target[0] is not a_target[0]:
         raise ValueError("the two ranges must lie in the same resident genome")
-    a_where, na, a_end, _a_keep = _matrix_range(a_target, *a_range)
-    b_where, nb, b_end, _b_keep = _matrix_range(b_target, *b_range)
+    a_where, na, a_end, a_keep = _matrix_range(a_target, *a_range)
+    b_where, nb, b_end, b_keep = _matrix_range(b_target, *b_range)
     win, _ = _dot_window(na, nb, rows, cols, 0, None)
-    args = a_where + (a_range[0], a_end) + b_where + (b_range[0], b_end, STRANDS[strand]) + win + (DIRECTIONS[directions], min_len)
-    if one_shot:
-        fn, head, tail = ctx.lib.prf_dotpair_runs_seq, (ctx._h,), ()
-    else:
-        fn, head, tail = ctx.lib.prf_dotpair_runs_ex, (ctx._h, a_target[0]._h), (launch_cells,)
-    capacity = DOTRUN_DEFAULT_CAPACITY
+    args = a_where + (a_range[0], a_end) + b_where + (b_range[0], b_end, STRANDS[strand]) + win + (DIRECTIONS[directions],)
+    fn, head, tail = _list_entry(ctx, name, None if one_shot else a_target[0], launch_cells)
+    return fn, head, args + tuple(param[1] for param in params), tail, (a_keep, b_keep)
+
+
+def _period_list_args(ctx, name, target, begin, end, kmin, kmax, params, n_matches, positions, launch_cells):
+    """The same of a list product of the period lines of a range: target is (genome, contig) or one sequence.  params: the integers
+    behind `n_matches`."""
+    if isinstance(kmin, bool) or isinstance(kmax, bool) or not 1 <= operator.index(kmin) <= operator.index(kmax) <= 0xFFFFFFFF:
+        raise ValueError(f"periods {kmin} .. {kmax}: an empty range")
+    for param in params:
+        _int_check(*param)
+    lo, hi = (0, None) if positions is None else positions
+    if lo < 0 or (hi is not None and lo > hi):
+        raise ValueError(f"positions {lo} .. {hi}: an empty range is given as lo == hi")
+    where, _n, c_end, keep = _matrix_range(target, begin, end)
+    args = where + (begin, c_end, lo, END_OF_CONTIG if hi is None else hi, kmin, kmax, 1 if n_matches else 0)
+    fn, head, tail = _list_entry(ctx, name, None if keep is not None else target[0], launch_cells)
+    return fn, head, args + tuple(param[1] for param in params), tail, keep
+
+
+def _list_call(ctx, fn, head, args, tail, dtype, capacity, max_rows, noun, advice, with_stats, fields=None):
+    """The one path of the list products: calls once with `capacity` rows of room and once more with the exact number if there were
+    more.  Returns the rows (their `fields`, or all), or (rows, ScanStats) with_stats."""
+    import numpy as np
     while True:
-        out = np.zeros(max(1, capacity), dtype=DOTRUN_DTYPE)
+        out = np.zeros(max(1, capacity), dtype=dtype)
         n, stats = ctypes.c_uint64(0), ScanStats()
         _check(ctx.lib, fn(*head, *args, out.ctypes.data_as(ctypes.c_void_p), capacity, ctypes.byref(n), ctypes.byref(stats), *tail))
         if n.value <= capacity:
             break
-        if n.value > DOTRUN_MAX_ROWS:
-            raise PrfError(PRF_EUNSUPPORTED, f"{n.value} runs are more than one call returns ({DOTRUN_MAX_ROWS}): ask for a larger "
-                                             "min_len or for smaller windows")
+        if n.value > max_rows:
+            raise PrfError(PRF_EUNSUPPORTED, f"{n.value} {noun} are more than one call returns ({max_rows}): ask for a larger {advice}")
         capacity = n.value
-    runs = out[:n.value][["row", "col", "len", "dir"]].copy()
-    return (runs, stats) if with_stats else runs
+    rows = (out[:n.value] if fields is None else out[:n.value][fields]).copy()
+    return (rows, stats) if with_stats else rows
+
+
+def _runs(ctx, a_target, a_range, b_target, b_range, strand, directions, min_len, rows, cols, with_stats, launch_cells):
+    """The dotpair_runs calls; the rows lose their reserved field."""
+    *call, _keep = _pair_list_args(ctx, "prf_dotpair_runs", a_target, a_range, b_target, b_range, strand, directions,
+                                   [("min_len", min_len, 1)], rows, cols, launch_cells)
+    return _list_call(ctx, *call, DOTRUN_DTYPE, DOTRUN_DEFAULT_CAPACITY, DOTRUN_MAX_ROWS, "runs", "min_len or for smaller windows",
+                      with_stats, ["row", "col", "len", "dir"])
 
 
 def _chains(ctx, a_target, a_range, b_target, b_range, strand, directions, min_seed, max_gap, min_len, rows, cols, with_stats,
             launch_cells):
-    """The one path of the dotpair_chains calls, as _runs: once with DOTCHAIN_DEFAULT_CAPACITY rows of room and once more with the
-    exact number if there were more."""
-    import numpy as np
-    if strand not in STRANDS:
-        raise ValueError(f"strand is {strand!r}. It must be '+' or '-'.")
-    if directions not in DIRECTIONS:
-        raise ValueError(f"directions is {directions!r}. It must be 'main', 'anti' or 'both'.")
-    if isinstance(min_seed, bool) or operator.index(min_seed) < 1:
-        raise ValueError(f"min_seed is set to {min_seed}. It must be at least 1.")
-    if isinstance(max_gap, bool) or not 0 <= operator.index(max_gap) <= DOTCHAIN_MAX_GAP:
-        raise ValueError(f"max_gap is set to {max_gap}. It must be 0 .. {DOTCHAIN_MAX_GAP}.")
-    if isinstance(min_len, bool) or operator.index(min_len) < 0:
-        raise ValueError(f"min_len is set to {min_len}. It must be at least 0.")
-    one_shot = not isinstance(a_target, tuple)
-    if one_shot == isinstance(b_target, tuple):
-        raise ValueError("the two ranges must both be sequences or both lie in a genome")
-    if not one_shot and b_target[0] is not a_target[0]:
-        raise ValueError("the two ranges must lie in the same resident genome")
-    a_where, na, a_end, _a_keep = _matrix_range(a_target, *a_range)
-    b_where, nb, b_end, _b_keep = _matrix_range(b_target, *b_range)
-    win, _ = _dot_window(na, nb, rows, cols, 0, None)
-    args = a_where + (a_range[0], a_end) + b_where + (b_range[0], b_end, STRANDS[strand]) + win + (DIRECTIONS[directions], min_seed,
-                                                                                               max_gap, min_len)
-    if one_shot:
-        fn, head, tail = ctx.lib.prf_dotpair_chains_seq, (ctx._h,), ()
-    else:
-        fn, head, tail = ctx.lib.prf_dotpair_chains_ex, (ctx._h, a_target[0]._h), (launch_cells,)
-    capacity = DOTCHAIN_DEFAULT_CAPACITY
-    while True:
-        out = np.zeros(max(1, capacity), dtype=DOTCHAIN_DTYPE)
-        n, stats = ctypes.c_uint64(0), ScanStats()
-        _check(ctx.lib, fn(*head, *args, out.ctypes.data_as(ctypes.c_void_p), capacity, ctypes.byref(n), ctypes.byref(stats), *tail))
-        if n.value <= capacity:
-            break
-        if n.value > DOTCHAIN_MAX_ROWS:
-            raise PrfError(PRF_EUNSUPPORTED, f"{n.value} chains are more than one call returns ({DOTCHAIN_MAX_ROWS}): ask for a larger "
-                                             "min_seed or min_len or for smaller windows")
-        capacity = n.value
-    chains = out[:n.value].copy()
-    return (chains, stats) if with_stats else chains
+    """The dotpair_chains calls."""
+    *call, _keep = _pair_list_args(ctx, "prf_dotpair_chains", a_target, a_range, b_target, b_range, strand, directions,
+                                   [("min_seed", min_seed, 1), ("max_gap", max_gap, 0, DOTCHAIN_MAX_GAP), ("min_len", min_len, 0)],
+                                   rows, cols, launch_cells)
+    return _list_call(ctx, *call, DOTCHAIN_DTYPE, DOTCHAIN_DEFAULT_CAPACITY, DOTCHAIN_MAX_ROWS, "chains",
+                      "min_seed or min_len or for smaller windows", with_stats)
 
 
 def _links(ctx, a_target, a_range, b_target, b_range, strand, directions, min_seed, max_gap, max_shift, rows, cols, with_stats,
            launch_cells):
-    """The one path of the dotpair_links calls, as _chains: once with DOTLINK_DEFAULT_CAPACITY rows of room and once more with the
-    exact number if there were more."""
-    import numpy as np
-    if strand not in STRANDS:
-        raise ValueError(f"strand is {strand!r}. It must be '+' or '-'.")
-    if directions not in DIRECTIONS:
-        raise ValueError(f"directions is {directions!r}. It must be 'main', 'anti' or 'both'.")
-    if isinstance(min_seed, bool) or operator.index(min_seed) < 1:
-        raise ValueError(f"min_seed is set to {min_seed}. It must be at least 1.")
-    if isinstance(max_gap, bool) or not 0 <= operator.index(max_gap) <= DOTCHAIN_MAX_GAP:
-        raise ValueError(f"max_gap is set to {max_gap}. It must be 0 .. {DOTCHAIN_MAX_GAP}.")
-    if isinstance(max_shift, bool) or not 1 <= operator.index(max_shift) <= DOTLINK_MAX_SHIFT:
-        raise ValueError(f"max_shift is set to {max_shift}. It must be 1 .. {DOTLINK_MAX_SHIFT}.")
-    one_shot = not isinstance(a_target, tuple)
-    if one_shot == isinstance(b_target, tuple):
-        raise ValueError("the two ranges must both be sequences or both lie in a genome")
-    if not one_shot and b_target[0] is not a_target[0]:
-        raise ValueError("the two ranges must lie in the same resident genome")
-    a_where, na, a_end, _a_keep = _matrix_range(a_target, *a_range)
-    b_where, nb, b_end, _b_keep = _matrix_range(b_target, *b_range)
-    win, _ = _dot_window(na, nb, rows, cols, 0, None)
-    args = a_where + (a_range[0], a_end) + b_where + (b_range[0], b_end, STRANDS[strand]) + win + (DIRECTIONS[directions], min_seed,
-                                                                                               max_gap, max_shift)
-    if one_shot:
-        fn, head, tail = ctx.lib.prf_dotpair_links_seq, (ctx._h,), ()
-    else:
-        fn, head, tail = ctx.lib.prf_dotpair_links_ex, (ctx._h, a_target[0]._h), (launch_cells,)
-    capacity = DOTLINK_DEFAULT_CAPACITY
-    while True:
-        out = np.zeros(max(1, capacity), dtype=DOTLINK_DTYPE)
-        n, stats = ctypes.c_uint64(0), ScanStats()
-        _check(ctx.lib, fn(*head, *args, out.ctypes.data_as(ctypes.c_void_p), capacity, ctypes.byref(n), ctypes.byref(stats), *tail))
-        if n.value <= capacity:
-            break
-        if n.value > DOTCHAIN_MAX_ROWS:
-            raise PrfError(PRF_EUNSUPPORTED, f"{n.value} links are more than one call returns ({DOTCHAIN_MAX_ROWS}): ask for a larger "
-                                             "min_seed or for smaller windows")
-        capacity = n.value
-    links = out[:n.value].copy()
-    return (links, stats) if with_stats else links
+    """The dotpair_links calls."""
+    *call, _keep = _pair_list_args(ctx, "prf_dotpair_links", a_target, a_range, b_target, b_range, strand, directions,
+                                   [("min_seed", min_seed, 1), ("max_gap", max_gap, 0, DOTCHAIN_MAX_GAP),
+                                    ("max_shift", max_shift, 1, DOTLINK_MAX_SHIFT)], rows, cols, launch_cells)
+    return _list_call(ctx, *call, DOTLINK_DTYPE, DOTLINK_DEFAULT_CAPACITY, DOTCHAIN_MAX_ROWS, "links", "min_seed or for smaller windows",
+                      with_stats)
 
 
 def _period_chains(ctx, target, begin, end, kmin, kmax, min_seed, max_gap, min_len, n_matches, positions, with_stats, launch_cells):
-    """The one path of the period_chains calls, as _chains: target is (genome, contig) or one sequence; once with
-    PCHAIN_DEFAULT_CAPACITY rows of room and once more with the exact number if there were more."""
-    import numpy as np
-    if isinstance(kmin, bool) or isinstance(kmax, bool) or not 1 <= operator.index(kmin) <= operator.index(kmax) <= 0xFFFFFFFF:
-        raise ValueError(f"periods {kmin} .. {kmax}: an empty range")
-    if isinstance(min_seed, bool) or operator.index(min_seed) < 1:
-        raise ValueError(f"min_seed is set to {min_seed}. It must be at least 1.")
-    if isinstance(max_gap, bool) or not 0 <= operator.index(max_gap) <= DOTCHAIN_MAX_GAP:
-        raise ValueError(f"max_gap is set to {max_gap}. It must be 0 .. {DOTCHAIN_MAX_GAP}.")
-    if isinstance(min_len, bool) or operator.index(min_len) < 0:
-        raise ValueError(f"min_len is set to {min_len}. It must be at least 0.")
-    lo, hi = (0, None) if positions is None else positions
-    if lo < 0 or (hi is not None and lo > hi):
-        raise ValueError(f"positions {lo} .. {hi}: an empty range is given as lo == hi")
-    where, _n, c_end, keep = _matrix_range(target, begin, end)
-    args = where + (begin, c_end, lo, END_OF_CONTIG if hi is None else hi, kmin, kmax, 1 if n_matches else 0, min_seed, max_gap, min_len)
-    if keep is not None:
-        fn, head, tail = ctx.lib.prf_period_chains_seq, (ctx._h,), ()
-    else:
-        fn, head, tail = ctx.lib.prf_period_chains_ex, (ctx._h, target[0]._h), (launch_cells,)
-    capacity = PCHAIN_DEFAULT_CAPACITY
-    while True:
-        out = np.zeros(max(1, capacity), dtype=PCHAIN_DTYPE)
-        n, stats = ctypes.c_uint64(0), ScanStats()
-        _check(ctx.lib, fn(*head, *args, out.ctypes.data_as(ctypes.c_void_p), capacity, ctypes.byref(n), ctypes.byref(stats), *tail))
-        if n.value <= capacity:
-            break
-        if n.value > PCHAIN_MAX_ROWS:
-            raise PrfError(PRF_EUNSUPPORTED, f"{n.value} chains are more than one call returns ({PCHAIN_MAX_ROWS}): ask for a larger "
-                                             "min_seed or min_len, fewer periods or fewer positions")
-        capacity = n.value
-    chains = out[:n.value].copy()
-    return (chains, stats) if with_stats else chains
+    """The period_chains calls."""
+    *call, _keep = _period_list_args(ctx, "prf_period_chains", target, begin, end, kmin, kmax,
+                                     [("min_seed", min_seed, 1), ("max_gap", max_gap, 0, DOTCHAIN_MAX_GAP), ("min_len", min_len, 0)],
+                                     n_matches, positions, launch_cells)
+    return _list_call(ctx, *call, PCHAIN_DTYPE, PCHAIN_DEFAULT_CAPACITY, PCHAIN_MAX_ROWS, "chains",
+                      "min_seed or min_len, fewer periods or fewer positions", with_stats)
 
 
 def _period_links(ctx, target, begin, end, kmin, kmax, min_seed, max_gap, max_shift, n_matches, positions, with_stats, launch_cells):
-    """The one path of the period_links calls, as _period_chains: once with PLINK_DEFAULT_CAPACITY rows of room and once more with
-    the exact number if there were more."""
-    import numpy as np
-    if isinstance(kmin, bool) or isinstance(kmax, bool) or not 1 <= operator.index(kmin) <= operator.index(kmax) <= 0xFFFFFFFF:
-        raise ValueError(f"periods {kmin} .. {kmax}: an empty range")
-    if isinstance(min_seed, bool) or operator.index(min_seed) < 1:
-        raise ValueError(f"min_seed is set to {min_seed}. It must be at least 1.")
-    if isinstance(max_gap, bool) or not 0 <= operator.index(max_gap) <= DOTCHAIN_MAX_GAP:
-        raise ValueError(f"max_gap is set to {max_gap}. It must be 0 .. {DOTCHAIN_MAX_GAP}.")
-    if isinstance(max_shift, bool) or not 1 <= operator.index(max_shift) <= DOTLINK_MAX_SHIFT:
-        raise ValueError(f"max_shift is set to {max_shift}. It must be 1 .. {DOTLINK_MAX_SHIFT}.")
-    lo, hi = (0, None) if positions is None else positions
-    if lo < 0 or (hi is not None and lo > hi):
-        raise ValueError(f"positions {lo} .. {hi}: an empty range is given as lo == hi")
-    where, _n, c_end, keep = _matrix_range(target, begin, end)
-    args = where + (begin, c_end, lo, END_OF_CONTIG if hi is None else hi, kmin, kmax, 1 if n_matches else 0, min_seed, max_gap, max_shift)
-    if keep is not None:
-        fn, head, tail = ctx.lib.prf_period_links_seq, (ctx._h,), ()
-    else:
-        fn, head, tail = ctx.lib.prf_period_links_ex, (ctx._h, target[0]._h), (launch_cells,)
-    capacity = PLINK_DEFAULT_CAPACITY
-    while True:
-        out = np.zeros(max(1, capacity), dtype=PLINK_DTYPE)
-        n, stats = ctypes.c_uint64(0), ScanStats()
-        _check(ctx.lib, fn(*head, *args, out.ctypes.data_as(ctypes.c_void_p), capacity, ctypes.byref(n), ctypes.byref(stats), *tail))
-        if n.value <= capacity:
-            break
-        if n.value > PCHAIN_MAX_ROWS:
-            raise PrfError(PRF_EUNSUPPORTED, f"{n.value} links are more than one call returns ({PCHAIN_MAX_ROWS}): ask for a larger "
-                                             "min_seed, fewer periods or fewer positions")
-        capacity = n.value
-    links = out[:n.value].copy()
-    return (links, stats) if with_stats else links
+    """The period_links calls."""
+    *call, _keep = _period_list_args(ctx, "prf_period_links", target, begin, end, kmin, kmax,
+                                     [("min_seed", min_seed, 1), ("max_gap", max_gap, 0, DOTCHAIN_MAX_GAP),
+                                      ("max_shift", max_shift, 1, DOTLINK_MAX_SHIFT)], n_matches, positions, launch_cells)
+    return _list_call(ctx, *call, PLINK_DTYPE, PLINK_DEFAULT_CAPACITY, PCHAIN_MAX_ROWS, "links",
+                      "min_seed, fewer periods or fewer positions", with_stats)
 
 
 def join_period_chains(chains, links):

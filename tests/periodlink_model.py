@@ -80,6 +80,56 @@ def all_links(chains, min_seed, max_gap, max_shift, unique=None):
     return np.sort(rows, order=["start", "k"])
 
 
+def all_links_by_join(chains, min_seed, max_gap, max_shift):
+    """all_links for lists whose pairwise matrices would not fit (a million chains): the same candidates, keys and choices, but
+    the candidates are listed instead of tabulated.  X is a candidate for Y at shift s = k_Y - k_X and distance gi = t_s(Y) -
+    t_e(X) - 1, so for each (s, gi) that the rule admits X is the one chain of line k_Y - s that ends at t_s(Y) - 1 - gi: an exact
+    join (chains of one line end at different cells).  pred and succ are the smallest key of a column and of a row, at equal keys
+    the first chain in the list's order, as argmin chooses.  tests/test_periodlink_cpu.py pins it to all_links."""
+    if not len(chains):
+        return np.zeros(0, dtype=DTYPE)
+    assert int(chains["k"].min()) >= 1
+    t_s = chains["start"].astype(np.int64)
+    t_e = t_s + chains["len"].astype(np.int64) - 1
+    delta = chains["k"].astype(np.int64)
+    ov = min(min_seed - 1, OVERLAP)
+    width = int(t_e.max()) + OVERLAP + max_gap + max_shift + 2    # (line, end cell) as one number: above every cell asked for
+    ends = delta * width + t_e
+    by_end = np.argsort(ends, kind="stable")
+    sorted_ends = ends[by_end]
+    xs, ys, keys = [], [], []
+    for s in [d for d in range(-max_shift, max_shift + 1) if d]:
+        for g in range(-ov, max_gap + 1):
+            gi = g if s > 0 else g - s                              # g = min(gi, gi + s)
+            line, cell = delta - s, t_s - 1 - gi
+            ok = (line >= 1) & (cell >= 0)
+            wanted = line * width + cell
+            at = np.minimum(np.searchsorted(sorted_ends, wanted), len(chains) - 1)
+            ok &= sorted_ends[at] == wanted
+            m, o = max(g, 0), max(-g, 0)
+            xs.append(by_end[at][ok])
+            ys.append(np.flatnonzero(ok))
+            keys.append(np.full(int(ok.sum()), (((m + abs(s)) * 64 + abs(s)) * 32 + o) * 2 + (s < 0), dtype=np.int64))
+    x, y, key = np.concatenate(xs), np.concatenate(ys), np.concatenate(keys)
+    pred = np.full(len(chains), -1, dtype=np.int64)
+    succ = np.full(len(chains), -1, dtype=np.int64)
+    order = np.lexsort((x, key, y))                               # per Y: the smallest key, then the first chain
+    first = np.concatenate(([True], y[order][1:] != y[order][:-1])) if len(order) else np.zeros(0, dtype=bool)
+    pred[y[order][first]] = x[order][first]
+    order = np.lexsort((y, key, x))
+    first = np.concatenate(([True], x[order][1:] != x[order][:-1])) if len(order) else np.zeros(0, dtype=bool)
+    succ[x[order][first]] = y[order][first]
+    y = np.flatnonzero(pred >= 0)
+    y = y[succ[pred[y]] == y]
+    x = pred[y]
+    g = np.minimum(t_s[y] - t_e[x] - 1, t_s[y] - t_e[x] - 1 + delta[y] - delta[x])
+    rows = np.zeros(len(y), dtype=DTYPE)
+    rows["start"], rows["k"] = chains["start"][y], chains["k"][y]
+    rows["from_end"] = t_e[x]
+    rows["shift"], rows["gap"], rows["overlap"] = delta[y] - delta[x], np.maximum(g, 0), np.maximum(-g, 0)
+    return np.sort(rows, order=["start", "k"])
+
+
 def select(links, n, positions=None, kmin=1, kmax=None):
     """The filters of a call on a list of links, and its order."""
     lo, hi = (0, n) if positions is None else positions
@@ -91,13 +141,15 @@ def select(links, n, positions=None, kmin=1, kmax=None):
     return np.sort(links[keep], order=["start", "k"])
 
 
-def links(seq, kmin, kmax, min_seed, max_gap, max_shift, n_matches=False, begin=0, end=None, positions=None, sparse=False):
-    """The list of a call.  pred(Y) is chosen among the lines k_Y +- max_shift and succ(X) among k_X +- max_shift, so the links
+def links(seq, kmin, kmax, min_seed, max_gap, max_shift, n_matches=False, begin=0, end=None, positions=None, sparse=False,
+          pairwise=True):
+    """The list of a call; pairwise False: by all_links_by_join, for a million chains.  pred(Y) is chosen among the lines k_Y +- max_shift and succ(X) among k_X +- max_shift, so the links
     with k_Y <= kmax are decided by the lines up to kmax + 2 max_shift: the lines above are not looked at (ranges of thousands of
     positions with short seeds, where the pairwise matrices of the whole band would not fit)."""
     n = len(M._bytes(seq)[begin:end])
     top = None if kmax is None else kmax + 2 * max_shift
-    every = all_links(band_chains(seq, n_matches, min_seed, max_gap, begin, end, sparse, top), min_seed, max_gap, max_shift)
+    every = (all_links if pairwise else all_links_by_join)(band_chains(seq, n_matches, min_seed, max_gap, begin, end, sparse, top),
+                                                           min_seed, max_gap, max_shift)
     return select(every, n, positions, kmin, kmax)
 
 

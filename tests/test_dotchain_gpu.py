@@ -397,6 +397,22 @@ def test_capacity_counts_fills_or_leaves_the_destination_alone(three_contigs):
     assert rc == prf_native.PRF_EINVAL and "contig 3" in g.ctx.lib.prf_last_error().decode()
 
 
+def test_more_seeds_than_the_first_pass_has_room_for(ctx):
+    """The seeds are written into 2^20 rows of room at first and once more into the exact number (grow_once, csrc/list_host.h).
+    At min_seed = 1 every run start of the window is a seed, 3/16 per cell and direction of random ACGT: 1 800 x 1 900 cells hold
+    1.28 million, a fifth above 2^20.  Without gaps a chain is its seed, and min_len keeps the list short."""
+    seqs = [_random(1_800, 61), _random(1_900, 62)]
+    g = ctx.load(seqs, 64)
+    try:
+        got, st = g.dotpair_chains((0, 0, None), (1, 0, None), "+", "both", 1, 0, 6, with_stats=True)
+    finally:
+        g.free()
+    assert st.n_candidates > 1 << 20
+    want = C.chains(seqs[0], seqs[1], "+", 1, 0, 6)
+    assert len(want) > 1_000 and st.n_hits == len(want)
+    _same(got, want)
+
+
 def test_windows_add_up_to_the_whole_list(three_contigs):
     g, seqs = three_contigs
     a, b = (2, 2_944, 3_400), (1, 50_950, 51_500)                             # 456 x 550, U against its reverse complement

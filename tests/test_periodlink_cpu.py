@@ -147,6 +147,30 @@ def test_the_smallest_key_is_unique_and_degrees_are_at_most_one(sequences, model
         assert (links["start"].astype(np.int64) > links["from_end"].astype(np.int64) - min(min_seed - 1, L.OVERLAP)).all()
 
 
+def test_the_join_form_of_the_model_agrees_with_the_pairwise_one(sequences, modelled):
+    """all_links_by_join, which tests/test_periodlink_gpu.py needs for a million chains, against all_links: the fixture's triples
+    on every fourth sequence (the two with max_shift 32, 2 000 joins each, on every twelfth), and seeds of one and two cells, where
+    the chains lie densest (the GPU test's min_seed = 1, max_gap = 0 among them), on the first 100 letters of every third: the
+    pairwise matrices of a thousand chains."""
+    bad, found = [], 0
+    for (at, triple, n_matches), (links, _) in modelled.items():
+        if at % (12 if triple[2] == 32 else 4):
+            continue
+        got = L.all_links_by_join(L.band_chains(sequences[at], n_matches, *triple[:2]), *triple)
+        found += len(got)
+        if not L.same(got, links):
+            bad.append((at, triple, n_matches))
+    for at, s in enumerate(sequences[::3]):
+        for triple in ((1, 0, 2), (1, 1, 1), (2, 0, 3)):
+            chains = L.band_chains(s[:100], at % 2, *triple[:2])
+            got, want = L.all_links_by_join(chains, *triple), L.all_links(chains, *triple)
+            found += len(want)
+            if not L.same(got, want):
+                bad.append((at, triple))
+    assert not bad, f"{len(bad)} differ: {bad[:5]}"
+    assert found > 20_000
+
+
 def test_partitions_in_positions_and_in_k_add_up(sequences, modelled):
     rng = random.Random(17)
     for at, s in list(enumerate(sequences))[::3]:

@@ -280,6 +280,23 @@ def test_capacity_and_counting(ctx, three_contigs):  # noqa: F811
             assert (buf == 0xAB).all()
 
 
+def test_more_heads_than_the_first_pass_has_room_for(ctx):
+    """The heads are written into 2^20 rows of room at first and once more into the exact number (grow_once, csrc/list_host.h).
+    At min_seed = 1 and max_gap = 0 every run start of the window is a head, 3/16 per cell of random ACGT: 6 200 positions x
+    1 000 lines hold 1.16 million, a tenth above 2^20.  So many chains do not fit the model's pairwise matrices: its join form,
+    which tests/test_periodlink_cpu.py pins to them."""
+    seq = _random(7_000, 63)
+    g = ctx.load([seq], 64)
+    try:
+        got, st = g.period_links(0, 0, None, 1, 1_000, 1, 0, 1, positions=(0, 6_200), with_stats=True)
+    finally:
+        g.free()
+    assert st.n_candidates > 1 << 20
+    want = L.links(seq, 1, 1_000, 1, 0, 1, positions=(0, 6_200), pairwise=False)
+    assert len(want) > 100_000 and st.n_hits == len(want)
+    _same(got, want)
+
+
 # ---- 5. the neighbours are not disturbed ----
 
 def test_scans_and_the_other_products_are_not_disturbed(ctx):
