@@ -9,6 +9,9 @@ neighbour -- which has no size limit (a chromosome takes well under a second on 
 --chains-tsv lists the DIVERGED TANDEM REPEATS of the input instead: on every period line, exact runs of at least --min-seed
 positions joined across at most --max-gap mismatching ones; it needs neither --window nor an image:
     plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --chains-tsv repeats.tsv --min-seed 12 --max-gap 8
+With --consensus the list also says WHAT each repeat is: its consensus motif (the majority letter of every column), the identity
+against that motif, the motif's own smallest period and the catalogue key (least rotation of the motif or its reverse complement):
+    plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --chains-tsv repeats.tsv --min-seed 12 --max-gap 8 --consensus
 --groups-tsv lists the GAPPED tandem repeats: those chains joined across indels of at most --max-shift bases (the junctions
 between neighbouring period lines), one line per repeat with substitutions and indels:
     plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --groups-tsv vntr.tsv --min-seed 12 --max-gap 8 --max-shift 4
@@ -54,11 +57,27 @@ def build_parser():
     p.add_argument("--n-matches", action="store_true", help="With --chains-tsv or --groups-tsv: N matches N, as in the matrix (default: N never "
                                                             "matches, as in the scans).")
     p.add_argument("--chain-window", type=int, default=1 << 22, help="With --chains-tsv or --groups-tsv: start positions per call.")
+    p.add_argument("--consensus", action="store_true", help="With --chains-tsv: append four columns per repeat: the consensus motif "
+                                                            "(majority letter per column), the identity against it, the motif's "
+                                                            "primitive period and its canonical form (least rotation of the motif "
+                                                            "or its reverse complement).")
+    p.add_argument("--min-consensus-identity", type=float, help="With --consensus: keep repeats of at least this identity against "
+                                                                "their consensus motif.")
     return p
 
 
 def check_chain_args(args, parser):
     """The checks of the --chains-tsv and --groups-tsv arguments, which need no GPU."""
+    if args.consensus and args.groups_tsv:
+        parser.error("--consensus goes with --chains-tsv: the columns of a gapped repeat drift at an indel, and its consensus needs "
+                     "the phase of every chain")
+    if args.consensus and not args.chains_tsv:
+        parser.error("--consensus belongs to --chains-tsv")
+    if args.min_consensus_identity is not None:
+        if not args.consensus:
+            parser.error("--min-consensus-identity belongs to --consensus")
+        if not 0.0 <= args.min_consensus_identity <= 1.0:
+            parser.error(f"--min-consensus-identity is set to {args.min_consensus_identity}. It must be 0 .. 1.")
     if not args.groups_tsv:
         if args.max_shift is not None:
             parser.error("--max-shift belongs to --groups-tsv")
@@ -154,8 +173,41 @@ def chain_lines(chrom, begin, seq, rows):
                f"{seq[begin + start:begin + start + k].upper()}\n")
 
 
+def consensus_batches(ks, max_rows, max_letters):
+    """(first, one past last) of the batches of rows that one period_consensus call takes: at most max_rows rows and max_letters
+    letters (the sum of k) each.  A single row above max_letters is a batch of its own, for the library to refuse."""
+    first, letters = 0, 0
+    for at, k in enumerate(ks):
+        if at > first and (at - first >= max_rows or letters + k > max_letters):
+            yield first, at
+            first, letters = at, 0
+        letters += k
+    if len(ks) > first:
+        yield first, len(ks)
+
+
+def consensus_of(genome, begin, end, rows):
+    """(rows of prf_native.consensus_rows, motifs) of the rows of tandem_rows, sent in batches that respect both limits."""
+    import numpy as np
+    import prf_native
+    cons, motifs = [np.zeros(0, dtype=prf_native.CONSENSUS_DTYPE)], []
+    for a, b in consensus_batches(rows["k"].tolist(), prf_native.CONSENSUS_MAX_ROWS, prf_native.CONSENSUS_MAX_LETTERS):
+        part, text = genome.period_consensus(0, begin, end, rows[a:b])
+        cons.append(part)
+        motifs += text
+    return prf_native.consensus_rows(rows, np.concatenate(cons), motifs), motifs
+
+
+def consensus_columns(rows, motifs):
+    """The four columns --consensus appends to a --chains-tsv line, per row of prf_native.consensus_rows."""
+    import prf_native
+    for identity, primitive, motif in zip(rows["consensus_identity"].tolist(), rows["primitive"].tolist(), motifs):
+        yield f"\t{motif}\t{identity:.4f}\t{primitive}\t{prf_native.canonical_motif(motif)}\n"
+
+
 def list_chains(args, chrom, seq, begin, end, context=None):
-    """--chains-tsv: the interval in windows of --chain-window start positions, the lists concatenated."""
+    """--chains-tsv: the interval in windows of --chain-window start positions, the lists concatenated; with --consensus the
+    consensus of every repeat that is left, from the same resident genome."""
     import numpy as np
     import prf_native
     ctx = context if context is not None else prf_native.default_context()
@@ -164,14 +216,22 @@ def list_chains(args, chrom, seq, begin, end, context=None):
         parts = [genome.period_chains(0, begin, end, args.min_motif_size, args.max_motif_size, args.min_seed, args.max_gap,
                                       args.min_chain, args.n_matches, (at, min(at + args.chain_window, end - begin)))
                  for at in range(0, end - begin, args.chain_window)]
+        chains = np.concatenate(parts) if parts else np.zeros(0, dtype=prf_native.PCHAIN_DTYPE)
+        rows = prf_native.tandem_rows(chains, drop_multiples=not args.keep_multiples)
+        rows = rows[rows["identity"] >= args.min_identity]
+        if args.consensus:
+            named, motifs = consensus_of(genome, begin, end, rows)
     finally:
         genome.free()
-    chains = np.concatenate(parts) if parts else np.zeros(0, dtype=prf_native.PCHAIN_DTYPE)
-    rows = prf_native.tandem_rows(chains, drop_multiples=not args.keep_multiples)
-    rows = rows[rows["identity"] >= args.min_identity]
+    lines = list(chain_lines(chrom, begin, seq, rows))
+    if args.consensus:
+        lines = [line[:-1] + more for line, more in zip(lines, consensus_columns(named, motifs))]
+        if args.min_consensus_identity is not None:
+            keep = (named["consensus_identity"] >= args.min_consensus_identity).tolist()
+            lines = [line for line, kept in zip(lines, keep) if kept]
     with open(args.chains_tsv, "wt") as out:
-        out.writelines(chain_lines(chrom, begin, seq, rows))
-    print(f"Wrote {args.chains_tsv}: {len(rows)} repeats")
+        out.writelines(lines)
+    print(f"Wrote {args.chains_tsv}: {len(lines)} repeats")
 
 
 def group_lines(chrom, begin, seq, rows):

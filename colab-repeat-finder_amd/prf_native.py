@@ -172,6 +172,15 @@ TANDEM_GROUP_DTYPE = [("start", "<u8"), ("end", "<u8"), ("period", "<u4"), ("cop
 # one row of tandem_rows per repeat
 TANDEM_DTYPE = [("start", "<u8"), ("end", "<u8"), ("k", "<u4"), ("copies", "<f8"), ("identity", "<f8"), ("matches", "<u8"),
                 ("seeds", "<u4")]
+# the entry points of the consensus motifs of such repeats (include/prf_consensus.h, which prf.h includes)
+CONSENSUS_EXPORTS = ["prf_period_consensus", "prf_period_consensus_ex", "prf_period_consensus_seq"]
+REPEAT_DTYPE = [("start", "<u8"), ("end", "<u8"), ("k", "<u4"), ("reserved", "<u4")]                         # prf_repeat, 24 bytes
+CONSENSUS_DTYPE = [("offset", "<u8"), ("agree", "<u8"), ("acgt", "<u8"), ("k", "<u4"), ("reserved", "<u4")]  # prf_consensus, 32 bytes
+CONSENSUS_MAX_ROWS = 1 << 24         # PRF_CONSENSUS_MAX_ROWS
+CONSENSUS_MAX_LETTERS = 1 << 26      # PRF_CONSENSUS_MAX_LETTERS: the sum of k per call
+CONSENSUS_SLICE = 4096               # PRF_CONSENSUS_SLICE: positions per work item by default (an unmeasured guess)
+# one row of consensus_rows per repeat: TANDEM_DTYPE and what the consensus adds
+TANDEM_CONSENSUS_DTYPE = TANDEM_DTYPE + [("consensus_identity", "<f8"), ("primitive", "<u4")]
 DIRECTIONS = {"main": 1, "anti": 2, "both": 3}
 DOT_LAUNCH_CELLS = 1 << 36   # PRF_DOT_LAUNCH_CELLS
 DOT_MAX_CELLS = 1 << 42      # PRF_DOT_MAX_CELLS
@@ -305,6 +314,11 @@ def load_library():
         lib.prf_period_links.argtypes = [vp, vp, ctypes.c_uint32] + plinks_tail
         lib.prf_period_links_ex.argtypes = [vp, vp, ctypes.c_uint32] + plinks_tail + [ctypes.c_uint64]
         lib.prf_period_links_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + plinks_tail
+        # begin, end, rows, n_rows, dst, motifs, letters_capacity, counts, stats
+        consensus_tail = [ctypes.c_uint64] * 2 + [vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, vp, ctypes.POINTER(ScanStats)]
+        lib.prf_period_consensus.argtypes = [vp, vp, ctypes.c_uint32] + consensus_tail
+        lib.prf_period_consensus_ex.argtypes = [vp, vp, ctypes.c_uint32] + consensus_tail + [ctypes.c_uint64]
+        lib.prf_period_consensus_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + consensus_tail
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
         lib.prf_measure_hbm_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -612,6 +626,94 @@ def _period_links(ctx, target, begin, end, kmin, kmax, min_seed, max_gap, max_sh
                                       ("max_shift", max_shift, 1, DOTLINK_MAX_SHIFT)], n_matches, positions, launch_cells)
     return _list_call(ctx, *call, PLINK_DTYPE, PLINK_DEFAULT_CAPACITY, PCHAIN_MAX_ROWS, "links",
                       "min_seed, fewer periods or fewer positions", with_stats)
+
+
+def _period_consensus(ctx, target, begin, end, repeats, counts, with_stats, slice_positions):
+    """The period_consensus calls.  target: (genome, contig) or one sequence.  Returns (rows of CONSENSUS_DTYPE, list of str), then
+    the counts as an array of (sum of k, 4) if asked, then the ScanStats with_stats."""
+    import numpy as np
+    try:
+        start, stop, k = (np.asarray(repeats[name]) for name in ("start", "end", "k"))
+    except (KeyError, ValueError, IndexError, TypeError):
+        raise ValueError("repeats must be a structured array with the fields start, end and k") from None
+    _int_check("slice_positions", slice_positions, 0)
+    n_rows = len(start)
+    if n_rows > CONSENSUS_MAX_ROWS:
+        raise ValueError(f"{n_rows} repeats are more than one call takes ({CONSENSUS_MAX_ROWS}): send them in batches")
+    where, n, c_end, keep = _matrix_range(target, begin, end)
+    rows = np.zeros(max(1, n_rows), dtype=REPEAT_DTYPE)
+    letters = 0
+    if n_rows:
+        if (k < 1).any() or (k > 0xFFFFFFFF).any():
+            raise ValueError(f"repeat {int(np.argmax((k < 1) | (k > 0xFFFFFFFF)))}: k must be at least 1")
+        bad = (start < 0) | (start >= stop) | (stop > n)
+        if bad.any():
+            at = int(np.argmax(bad))
+            raise ValueError(f"repeat {at}: [{start[at]}, {stop[at]}) is not a stretch of the range's {n} positions")
+        rows["start"][:n_rows], rows["end"][:n_rows], rows["k"][:n_rows] = start, stop, k
+        letters = int(rows["k"][:n_rows].sum(dtype=np.uint64))
+        if letters > CONSENSUS_MAX_LETTERS:
+            raise ValueError(f"the k of the repeats add up to {letters}, more than one call takes ({CONSENSUS_MAX_LETTERS}): send them in batches")
+    out = np.zeros(max(1, n_rows), dtype=CONSENSUS_DTYPE)
+    motifs = np.zeros(max(1, letters), dtype=np.uint8)
+    table = np.zeros((max(1, letters), 4), dtype=np.uint32) if counts else None
+    stats = ScanStats()
+    if keep is not None:
+        fn, head, tail = ctx.lib.prf_period_consensus_seq, (ctx._h,), ()
+    else:
+        fn, head, tail = ctx.lib.prf_period_consensus_ex, (ctx._h, target[0]._h), (slice_positions,)
+    _check(ctx.lib, fn(*head, *where, begin, c_end, rows.ctypes.data, n_rows, out.ctypes.data, motifs.ctypes.data, letters,
+                       table.ctypes.data if counts else None, ctypes.byref(stats), *tail))
+    text = motifs[:letters].tobytes().decode("ascii")
+    got = out[:n_rows].copy()
+    result = (got, [text[o:o + kk] for o, kk in zip(got["offset"].tolist(), got["k"].tolist())])
+    if counts:
+        result += (table[:letters],)
+    return result + (stats,) if with_stats else result
+
+
+def primitive_period(motif):
+    """The smallest divisor d of len(motif) for which the motif is d-periodic (motif == motif[:d] * (len / d))."""
+    k = len(motif)
+    for d in range(1, k + 1):
+        if k % d == 0 and motif[:d] * (k // d) == motif:
+            return d
+    return 0
+
+
+_COMPLEMENT = str.maketrans("ACGTN", "TGCAN")
+
+
+def canonical_motif(motif):
+    """The catalogue key of a motif over A, C, G, T, N: the lexicographically least string among the rotations of the motif and of
+    its reverse complement (N pairs with N).  Two loci of one satellite, read from any phase and either strand, share it."""
+    motif = motif.upper()
+    if set(motif) - set("ACGTN"):
+        raise ValueError(f"a motif over A, C, G, T, N is needed, not {motif!r}")
+    if not motif:
+        return motif
+    best = None
+    for text in (motif, motif.translate(_COMPLEMENT)[::-1]):
+        twice = text + text
+        least = min(twice[i:i + len(text)] for i in range(len(text)))
+        best = least if best is None or least < best else best
+    return best
+
+
+def consensus_rows(tandem, cons, motifs):
+    """The repeats of tandem_rows with what period_consensus says of them, one row of TANDEM_CONSENSUS_DTYPE each, in their order:
+    the fields of TANDEM_DTYPE, consensus_identity = agree / (end - start) (copy against motif, where identity is copy against the
+    copy in front) and primitive = the smallest period of the consensus motif itself.  Host numpy."""
+    import numpy as np
+    if not (len(tandem) == len(cons) == len(motifs)) or (len(cons) and (cons["k"] != tandem["k"]).any()):
+        raise ValueError("consensus_rows needs the rows period_consensus returned for these repeats")
+    out = np.zeros(len(tandem), dtype=TANDEM_CONSENSUS_DTYPE)
+    for name, _ in TANDEM_DTYPE:
+        out[name] = tandem[name]
+    span = (tandem["end"] - tandem["start"]).astype(np.float64)
+    out["consensus_identity"] = cons["agree"].astype(np.float64) / np.maximum(span, 1.0)
+    out["primitive"] = [primitive_period(m) for m in motifs]
+    return out
 
 
 def join_period_chains(chains, links):
@@ -928,6 +1030,17 @@ class Genome:
         return _period_links(self.ctx, (self, contig), begin, end, kmin, kmax, min_seed, max_gap, max_shift, n_matches, positions,
                              with_stats, launch_cells)
 
+    def period_consensus(self, contig, begin, end, repeats, counts=False, with_stats=False, slice_positions=0):
+        """The CONSENSUS MOTIFS of repeats of positions [begin, end) of a contig (prf_period_consensus).  repeats: any structured
+        array with the fields start, end (relative to begin) and k, such as the rows of tandem_rows().  Column p of a repeat holds
+        the positions start + p + j k; its letter is the most frequent of A, C, G, T there (ties to the first in that order, 'N'
+        for a column without any).  Returns (rows, motifs) in the order of the repeats: a numpy structured array with the fields
+        offset, agree (positions that carry their column's letter), acgt (positions that are A, C, G or T) and k, and the motifs
+        as a list of str; with counts=True also the counts, an array of (sum of k, 4) at the rows' offsets.  end None: the
+        contig's end.  slice_positions: positions per work item (0: the default), for the tests.  consensus_rows() joins the
+        result to the repeats."""
+        return _period_consensus(self.ctx, (self, contig), begin, end, repeats, counts, with_stats, slice_positions)
+
     @property
     def positions(self):
         return self.ctx.lib.prf_genome_positions(self._h)
@@ -1140,6 +1253,10 @@ class Context:
                       with_stats=False):
         """Genome.period_chains for one sequence (str or bytes) in one call: load, list, free (prf_period_chains_seq)."""
         return _period_chains(self, seq, begin, end, kmin, kmax, min_seed, max_gap, min_len, n_matches, positions, with_stats, 0)
+
+    def period_consensus(self, seq, repeats, begin=0, end=None, counts=False, with_stats=False):
+        """Genome.period_consensus for one sequence (str or bytes) in one call: load, count, free (prf_period_consensus_seq)."""
+        return _period_consensus(self, seq, begin, end, repeats, counts, with_stats, 0)
 
     def period_links(self, seq, kmin, kmax, min_seed, max_gap, max_shift, n_matches=False, begin=0, end=None, positions=None,
                      with_stats=False):

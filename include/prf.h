@@ -361,6 +361,10 @@ int prf_measure_hbm_read(prf_ctx *ctx, uint64_t bytes, int iters, double *gbps);
  * to ABI version 4, declared in prf_periodlink.h, which this header includes here; prf_scan_stats.path = 11 is theirs. */
 #include "prf_periodlink.h"
 
+/* ---- the consensus motifs of such repeats: what each column of a repeat of period k holds: three more entry points,
+ * additions to ABI version 4, declared in prf_consensus.h, which this header includes here; prf_scan_stats.path = 12 is theirs. */
+#include "prf_consensus.h"
+
 #ifdef __cplusplus
 }
 #endif
