@@ -13,9 +13,10 @@
 //                              end the wave sweeps the columns it touched: one add per (column, base) that is not 0
 //   larger k                   the adds of a step go straight to the global counts: 64 different columns per step
 // prf_consensus_finish_kernel, one wave per row: the letter of every column, and agree and acgt by a wave reduction.
-// No address into the planes is formed here but in cs_wave_source::take.
+// No address into the planes is formed here but in cs_wave_source::take (consensus_wave.h, shared with phased.hip).
 #include "../../include/prf.h"
 #include "consensus_launch.h"
+#include "consensus_wave.h"
 
 #define CS_THREADS 256
 #define CS_WAVES (CS_THREADS / 64)
@@ -25,37 +26,6 @@ static_assert(sizeof(prf_repeat) == 24 && sizeof(cs_row) == 32 && sizeof(cs_item
 static_assert(PRF_CS_REG_K == 64u && PRF_CS_LDS_K > 64u, "the lanes of a step of k > 64 hit different columns");
 
 namespace {
-
-// cs_count_item's source: the words of the planes, 64 at a time.  `last` is the last word that holds a position of the item;
-// every lane of the wave calls take with the same w.
-struct cs_wave_source {
-    const prf_planes &pl;
-    const u64 last;
-    const u32 lane;
-    u64 base = 0;
-    bool loaded = false;
-    u64 mine[3] = {0, 0, 0};
-    __device__ __forceinline__ void take(u64 w, u64 *out) {
-        if (!loaded || w - base >= 64ull) {
-            base = w;
-            loaded = true;
-            const u64 my = w + lane;
-            const bool in = my <= last;
-            mine[0] = in ? pl.H[my] : 0ull;
-            mine[1] = in ? pl.L[my] : 0ull;
-            mine[2] = in ? pl.X[my] : 0ull;
-        }
-#pragma unroll
-        for (int p = 0; p < 3; p++) out[p] = __shfl(mine[p], (int)(w - base));
-    }
-};
-
-// between the phases of a wave's LDS region: what the lanes wrote is what the lanes read
-__device__ __forceinline__ void cs_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 template <int REGIME>
 __global__ __launch_bounds__(CS_THREADS) void prf_consensus_count_kernel(const prf_consensus_args a, const u64 item0, const u64 n_items) {

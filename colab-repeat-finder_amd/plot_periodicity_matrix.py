@@ -15,6 +15,9 @@ against that motif, the motif's own smallest period and the catalogue key (least
 --groups-tsv lists the GAPPED tandem repeats: those chains joined across indels of at most --max-shift bases (the junctions
 between neighbouring period lines), one line per repeat with substitutions and indels:
     plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --groups-tsv vntr.tsv --min-seed 12 --max-gap 8 --max-shift 4
+With --group-consensus that list says WHAT each gapped repeat is as well: the consensus motif of its largest piece (the stretch
+over which isolated indels decide the column of every base), counted over segments with a phase:
+    plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --groups-tsv vntr.tsv --min-seed 12 --max-gap 8 --max-shift 4 --group-consensus
 """
 import argparse
 import os
@@ -63,6 +66,13 @@ def build_parser():
                                                             "or its reverse complement).")
     p.add_argument("--min-consensus-identity", type=float, help="With --consensus: keep repeats of at least this identity against "
                                                                 "their consensus motif.")
+    p.add_argument("--group-consensus", action="store_true", help="With --groups-tsv: append six columns per repeat: the consensus "
+                                                                  "motif of its largest piece, the identity against it, the "
+                                                                  "motif's primitive period, its canonical form, the number of "
+                                                                  "pieces the repeat was cut into and the share of the repeat "
+                                                                  "that the chosen piece covers.")
+    p.add_argument("--min-group-consensus-identity", type=float, help="With --group-consensus: keep repeats of at least this "
+                                                                      "identity against their consensus motif.")
     return p
 
 
@@ -78,6 +88,13 @@ def check_chain_args(args, parser):
             parser.error("--min-consensus-identity belongs to --consensus")
         if not 0.0 <= args.min_consensus_identity <= 1.0:
             parser.error(f"--min-consensus-identity is set to {args.min_consensus_identity}. It must be 0 .. 1.")
+    if args.group_consensus and not args.groups_tsv:
+        parser.error("--group-consensus belongs to --groups-tsv")
+    if args.min_group_consensus_identity is not None:
+        if not args.group_consensus:
+            parser.error("--min-group-consensus-identity belongs to --group-consensus")
+        if not 0.0 <= args.min_group_consensus_identity <= 1.0:
+            parser.error(f"--min-group-consensus-identity is set to {args.min_group_consensus_identity}. It must be 0 .. 1.")
     if not args.groups_tsv:
         if args.max_shift is not None:
             parser.error("--max-shift belongs to --groups-tsv")
@@ -241,9 +258,56 @@ def group_lines(chrom, begin, seq, rows):
                f"{seq[begin + start:begin + start + period].upper()}\n")
 
 
+def piece_batches(ks, segments, max_rows, max_letters, max_segments):
+    """(first, one past last) of the batches of pieces that one phased_consensus call takes: at most max_rows rows, max_letters
+    letters (the sum of k) and max_segments segments each; segments[i] is the number of segments of piece i.  A single piece
+    above a limit is a batch of its own, for the library to refuse."""
+    first, letters, n_segments = 0, 0, 0
+    for at, (k, n) in enumerate(zip(ks, segments)):
+        if at > first and (at - first >= max_rows or letters + k > max_letters or n_segments + n > max_segments):
+            yield first, at
+            first, letters, n_segments = at, 0, 0
+        letters, n_segments = letters + k, n_segments + n
+    if len(ks) > first:
+        yield first, len(ks)
+
+
+def group_consensus_of(genome, begin, end, joined, keep, chains, links):
+    """(rows of prf_native.group_consensus_rows, motifs) of all groups of joined = join_period_chains(chains, links,
+    with_paths=True); only the pieces of the groups whose `keep` is set are counted, in batches that respect the limits of one call, the others stay empty."""
+    import numpy as np
+    import prf_native
+    groups = joined[0]
+    pieces, segments = prf_native.group_segments(chains, links, joined)
+    wanted = keep[pieces["group"].astype(np.int64)] if len(pieces) else np.zeros(0, dtype=bool)
+    new_row = np.cumsum(wanted) - 1                                              # of a wanted piece among the wanted ones
+    pieces = pieces[wanted]
+    segments = segments[wanted[segments["row"].astype(np.int64)]] if len(segments) else segments
+    segments["row"] = new_row[segments["row"].astype(np.int64)] if len(segments) else segments["row"]
+    cons, motifs = [np.zeros(0, dtype=prf_native.CONSENSUS_DTYPE)], []
+    seg0 = np.concatenate([[0], np.cumsum(pieces["segments"].astype(np.int64))])    # a piece's segments are consecutive
+    for a, b in piece_batches(pieces["k"].tolist(), pieces["segments"].tolist(), prf_native.CONSENSUS_MAX_ROWS,
+                              prf_native.CONSENSUS_MAX_LETTERS, prf_native.PHASED_MAX_SEGMENTS):
+        part = segments[seg0[a]:seg0[b]].copy()
+        part["row"] -= a
+        rows, text = genome.phased_consensus(0, begin, end, pieces["k"][a:b], part)
+        cons.append(rows)
+        motifs += text
+    return prf_native.group_consensus_rows(groups, pieces, np.concatenate(cons), motifs)
+
+
+def group_consensus_columns(rows, motifs):
+    """The six columns --group-consensus appends to a --groups-tsv line, per row of prf_native.group_consensus_rows."""
+    import prf_native
+    for identity, primitive, pieces, covered, motif in zip(rows["consensus_identity"].tolist(), rows["primitive"].tolist(),
+                                                           rows["pieces"].tolist(), rows["covered"].tolist(), motifs):
+        yield f"\t{motif}\t{identity:.4f}\t{primitive}\t{prf_native.canonical_motif(motif)}\t{pieces}\t{covered:.4f}\n"
+
+
 def list_groups(args, chrom, seq, begin, end, context=None):
     """--groups-tsv: the interval in windows of --chain-window start positions; per window the chains (min_len 0) and the links,
-    which add up over the windows; then the join, the filters and one line per group."""
+    which add up over the windows; then the join, the filters and one line per group; with --group-consensus the consensus of
+    every repeat that is left, from the same resident genome."""
     import numpy as np
     import prf_native
     ctx = context if context is not None else prf_native.default_context()
@@ -256,16 +320,29 @@ def list_groups(args, chrom, seq, begin, end, context=None):
                                                args.n_matches, window))
             links.append(genome.period_links(0, begin, end, args.min_motif_size, args.max_motif_size, args.min_seed, args.max_gap,
                                              args.max_shift, args.n_matches, window))
+        chains = np.concatenate(chains) if chains else np.zeros(0, dtype=prf_native.PCHAIN_DTYPE)
+        links = np.concatenate(links) if links else np.zeros(0, dtype=prf_native.PLINK_DTYPE)
+        joined = prf_native.join_period_chains(chains, links, with_paths=True)
+        groups = joined[0]
+        rows, kept = prf_native.tandem_groups(groups, drop_covered=not args.keep_covered, with_index=True)
+        passed = (rows["end"] - rows["start"] >= args.min_group) & (rows["identity"] >= args.min_identity)
+        rows, kept = rows[passed], kept[passed]
+        if args.group_consensus:
+            keep = np.zeros(len(groups), dtype=bool)
+            keep[kept] = True
+            named, motifs = group_consensus_of(genome, begin, end, joined, keep, chains, links)
+            named, motifs = named[kept], [motifs[at] for at in kept.tolist()]
     finally:
         genome.free()
-    chains = np.concatenate(chains) if chains else np.zeros(0, dtype=prf_native.PCHAIN_DTYPE)
-    links = np.concatenate(links) if links else np.zeros(0, dtype=prf_native.PLINK_DTYPE)
-    groups = prf_native.join_period_chains(chains, links)
-    rows = prf_native.tandem_groups(groups, drop_covered=not args.keep_covered)
-    rows = rows[(rows["end"] - rows["start"] >= args.min_group) & (rows["identity"] >= args.min_identity)]
+    lines = list(group_lines(chrom, begin, seq, rows))
+    if args.group_consensus:
+        lines = [line[:-1] + more for line, more in zip(lines, group_consensus_columns(named, motifs))]
+        if args.min_group_consensus_identity is not None:
+            passed = (named["consensus_identity"] >= args.min_group_consensus_identity).tolist()
+            lines = [line for line, ok in zip(lines, passed) if ok]
     with open(args.groups_tsv, "wt") as out:
-        out.writelines(group_lines(chrom, begin, seq, rows))
-    print(f"Wrote {args.groups_tsv}: {len(rows)} repeats")
+        out.writelines(lines)
+    print(f"Wrote {args.groups_tsv}: {len(lines)} repeats")
 
 
 def main(argv=None, context=None):

@@ -181,6 +181,14 @@ CONSENSUS_MAX_LETTERS = 1 << 26      # PRF_CONSENSUS_MAX_LETTERS: the sum of k p
 CONSENSUS_SLICE = 4096               # PRF_CONSENSUS_SLICE: positions per work item by default (an unmeasured guess)
 # one row of consensus_rows per repeat: TANDEM_DTYPE and what the consensus adds
 TANDEM_CONSENSUS_DTYPE = TANDEM_DTYPE + [("consensus_identity", "<f8"), ("primitive", "<u4")]
+# the entry points of the consensus motifs over segments with a phase (include/prf_phased.h, which prf.h includes)
+PHASED_EXPORTS = ["prf_phased_consensus", "prf_phased_consensus_ex", "prf_phased_consensus_seq"]
+SEGMENT_DTYPE = [("start", "<u8"), ("end", "<u8"), ("row", "<u4"), ("phase", "<u4")]                          # prf_segment, 24 bytes
+PHASED_MAX_SEGMENTS = 1 << 24        # PRF_PHASED_MAX_SEGMENTS
+# one row of group_segments' pieces per consensus row of a gapped repeat
+PIECE_DTYPE = [("group", "<u8"), ("anchor", "<u8"), ("end", "<u8"), ("k", "<u4"), ("segments", "<u4"), ("positions", "<u8")]
+# one row of group_consensus_rows per gapped repeat: TANDEM_GROUP_DTYPE and what the consensus of its largest piece adds
+GROUP_CONSENSUS_DTYPE = TANDEM_GROUP_DTYPE + [("consensus_identity", "<f8"), ("primitive", "<u4"), ("pieces", "<u4"), ("covered", "<f8")]
 DIRECTIONS = {"main": 1, "anti": 2, "both": 3}
 DOT_LAUNCH_CELLS = 1 << 36   # PRF_DOT_LAUNCH_CELLS
 DOT_MAX_CELLS = 1 << 42      # PRF_DOT_MAX_CELLS
@@ -319,6 +327,11 @@ def load_library():
         lib.prf_period_consensus.argtypes = [vp, vp, ctypes.c_uint32] + consensus_tail
         lib.prf_period_consensus_ex.argtypes = [vp, vp, ctypes.c_uint32] + consensus_tail + [ctypes.c_uint64]
         lib.prf_period_consensus_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + consensus_tail
+        # begin, end, ks, n_rows, segments, n_segments, dst, motifs, letters_capacity, counts, stats
+        phased_tail = consensus_tail[:4] + [vp, ctypes.c_uint64] + consensus_tail[4:]
+        lib.prf_phased_consensus.argtypes = [vp, vp, ctypes.c_uint32] + phased_tail
+        lib.prf_phased_consensus_ex.argtypes = [vp, vp, ctypes.c_uint32] + phased_tail + [ctypes.c_uint64]
+        lib.prf_phased_consensus_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + phased_tail
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
         lib.prf_measure_hbm_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -672,6 +685,178 @@ def _period_consensus(ctx, target, begin, end, repeats, counts, with_stats, slic
     return result + (stats,) if with_stats else result
 
 
+def _phased_consensus(ctx, target, begin, end, ks, segments, counts, with_stats, slice_positions):
+    """The phased_consensus calls.  target: (genome, contig) or one sequence.  Returns what _period_consensus returns."""
+    import numpy as np
+    try:
+        k = np.asarray(ks)
+        if k.ndim != 1 or (len(k) and k.dtype.kind not in "iu"):
+            raise TypeError
+    except (ValueError, TypeError):
+        raise ValueError("ks must be a sequence of integers, one k per row") from None
+    try:
+        start, stop, row, phase = (np.asarray(segments[name]) for name in ("start", "end", "row", "phase"))
+    except (KeyError, ValueError, IndexError, TypeError):
+        raise ValueError("segments must be a structured array with the fields start, end, row and phase") from None
+    _int_check("slice_positions", slice_positions, 0)
+    n_rows, n_segments = len(k), len(start)
+    if n_rows > CONSENSUS_MAX_ROWS:
+        raise ValueError(f"{n_rows} rows are more than one call takes ({CONSENSUS_MAX_ROWS}): send them in batches")
+    if n_segments > PHASED_MAX_SEGMENTS:
+        raise ValueError(f"{n_segments} segments are more than one call takes ({PHASED_MAX_SEGMENTS}): send them in batches")
+    where, n, c_end, keep = _matrix_range(target, begin, end)
+    widths = np.zeros(max(1, n_rows), dtype=np.uint32)
+    table = np.zeros(max(1, n_segments), dtype=SEGMENT_DTYPE)
+    letters = 0
+    if n_rows:
+        if (k < 1).any() or (k > 0xFFFFFFFF).any():
+            raise ValueError(f"row {int(np.argmax((k < 1) | (k > 0xFFFFFFFF)))}: k must be at least 1")
+        widths[:n_rows] = k
+        letters = int(widths[:n_rows].sum(dtype=np.uint64))
+        if letters > CONSENSUS_MAX_LETTERS:
+            raise ValueError(f"the k of the rows add up to {letters}, more than one call takes ({CONSENSUS_MAX_LETTERS}): send them in batches")
+    if n_segments:
+        bad = (start < 0) | (start >= stop) | (stop > n)
+        if bad.any():
+            at = int(np.argmax(bad))
+            raise ValueError(f"segment {at}: [{start[at]}, {stop[at]}) is not a stretch of the range's {n} positions")
+        bad = (row < 0) | (row >= n_rows)
+        if bad.any():
+            at = int(np.argmax(bad))
+            raise ValueError(f"segment {at}: row {row[at]} is not one of the {n_rows} rows")
+        bad = (phase < 0) | (phase >= widths[:n_rows][row.astype(np.int64)])
+        if bad.any():
+            at = int(np.argmax(bad))
+            raise ValueError(f"segment {at}: phase {phase[at]} is not below the k = {widths[int(row[at])]} of row {row[at]}")
+        table["start"], table["end"], table["row"], table["phase"] = start, stop, row, phase
+    out = np.zeros(max(1, n_rows), dtype=CONSENSUS_DTYPE)
+    motifs = np.zeros(max(1, letters), dtype=np.uint8)
+    sums = np.zeros((max(1, letters), 4), dtype=np.uint32) if counts else None
+    stats = ScanStats()
+    if keep is not None:
+        fn, head, tail = ctx.lib.prf_phased_consensus_seq, (ctx._h,), ()
+    else:
+        fn, head, tail = ctx.lib.prf_phased_consensus_ex, (ctx._h, target[0]._h), (slice_positions,)
+    _check(ctx.lib, fn(*head, *where, begin, c_end, widths.ctypes.data, n_rows, table.ctypes.data, n_segments, out.ctypes.data,
+                       motifs.ctypes.data, letters, sums.ctypes.data if counts else None, ctypes.byref(stats), *tail))
+    text = motifs[:letters].tobytes().decode("ascii")
+    got = out[:n_rows].copy()
+    result = (got, [text[o:o + kk] for o, kk in zip(got["offset"].tolist(), got["k"].tolist())])
+    if counts:
+        result += (sums[:letters],)
+    return result + (stats,) if with_stats else result
+
+
+def _link_paths(chains, links):
+    """(paths, link_out, is_open) of the chains of period_chains (min_len = 0) and the links of period_links of the same window
+    and settings: every chain has at most one link in and one out, so the links form paths.  paths: one list of chain indices per
+    path, in the order of the paths' first chains; link_out[x]: the index of the link that leaves chain x, or -1; is_open[y]: a
+    link into chain y names a predecessor that is not in `chains`.  The one place where links are resolved to chains."""
+    n = len(chains)
+    start, length, line = (chains[f].astype("int64").tolist() for f in ("start", "len", "k"))
+    first = {key: at for at, key in enumerate(zip(start, line))}
+    last = {(s + l - 1, k): at for at, (s, l, k) in enumerate(zip(start, length, line))}
+    nxt, link_out, has_in, is_open = [-1] * n, [-1] * n, [False] * n, [False] * n
+    for at, (t_s, t_e, k, s) in enumerate(zip(*(links[f].tolist() for f in ("start", "from_end", "k", "shift")))):
+        y = first.get((t_s, k))
+        if y is None:
+            raise ValueError(f"the link into (start {t_s}, k {k}) names a successor that is not in the list of chains: "
+                             "join_period_chains needs the chains of the same window, range of k, min_seed and max_gap, fetched at min_len = 0")
+        x = last.get((t_e, k - s))
+        if x is None:
+            is_open[y] = True
+        else:
+            nxt[x], link_out[x], has_in[y] = y, at, True
+    paths = []
+    for head in range(n):
+        if has_in[head]:
+            continue
+        path, cur = [], head
+        while cur >= 0:
+            path.append(cur)
+            cur = nxt[cur]
+        paths.append(path)
+    return paths, link_out, is_open
+
+
+def period_paths(chains, links):
+    """The paths join_period_chains folds into groups, in its order: one list of chain indices per group."""
+    return _link_paths(chains, links)[0]
+
+
+def group_segments(chains, links, joined=None):
+    """The PHASED SEGMENTS of the gapped repeats of join_period_chains(chains, links) (the same inputs): what phased_consensus needs
+    to name them.  joined: what join_period_chains(chains, links, with_paths=True) returned, if the caller has it (else the join
+    is made here).  Returns (pieces, segments): rows of PIECE_DTYPE and of SEGMENT_DTYPE; segment.row indexes pieces, and the
+    segments of a piece are consecutive, in ascending order, and disjoint.
+    Per path, with P the group's period: only the chains on line P give positions, [start, start + len + P) each.  The first opens
+    a PIECE, one consensus row of k = P whose column 0 is the piece's first position (anchor).  Between two consecutive on-period
+    chains A and B of the path: exactly one chain Y with len_Y <= k_Y in between is an isolated indel of k_Y - P bases (negative: a
+    deletion) -- B continues the piece, its columns moved by the piece's drift D += k_Y - P, and the inserted bases fall in no
+    column; anything else (two or more chains in between, or a Y longer than its line) leaves the phase undecided: the piece ends
+    and B opens a new one.  A chain's segment begins where the piece's previous segment ended if they overlap, and is dropped if
+    nothing is left; its phase is (segment start - anchor - D) mod P.  Chains in front of the first or behind the last on-period
+    chain give nothing.  pieces: group (the index into join_period_chains' rows), anchor, end (of the last segment), k,
+    segments, positions (the sum of the segments' lengths).  Host numpy."""
+    import numpy as np
+    groups, paths = joined if joined is not None else join_period_chains(chains, links, with_paths=True)
+    start, length, line = (chains[f].astype(np.int64).tolist() for f in ("start", "len", "k"))
+    pieces, segments = [], []
+    for at, (path, period) in enumerate(zip(paths, groups["period"].tolist())):
+        on = [j for j, c in enumerate(path) if line[c] == period]
+        piece = None                                           # [group, anchor, end, k, segments, positions], drift alongside
+        drift = 0
+        for prev, j in zip([None] + on[:-1], on):
+            c = path[j]
+            between = [] if prev is None else path[prev + 1:j]
+            if piece is not None and len(between) == 1 and length[between[0]] <= line[between[0]]:
+                drift += line[between[0]] - period
+            else:
+                piece, drift = [at, start[c], start[c], period, 0, 0], 0
+                pieces.append(piece)
+            lo, hi = max(start[c], piece[2]), start[c] + length[c] + period
+            if lo >= hi:
+                continue
+            segments.append((lo, hi, len(pieces) - 1, (lo - piece[1] - drift) % period))
+            piece[2], piece[4], piece[5] = hi, piece[4] + 1, piece[5] + hi - lo
+    return (np.array([tuple(p) for p in pieces], dtype=PIECE_DTYPE).reshape(len(pieces)),
+            np.array(segments, dtype=SEGMENT_DTYPE).reshape(len(segments)))
+
+
+def group_consensus_rows(groups, pieces, cons, motifs):
+    """The gapped repeats of tandem_groups(join_period_chains(...), drop_covered=False) -- or the rows of join_period_chains
+    themselves -- with what phased_consensus says of the pieces group_segments cut them into.  Returns (rows of
+    GROUP_CONSENSUS_DTYPE, motifs as a list of str), one per group, in their order: the fields of TANDEM_GROUP_DTYPE; the motif of
+    the piece with the most positions (ties: the first); consensus_identity = agree / positions of that piece; primitive = the
+    smallest period of that motif; pieces = the group's number of pieces; covered = the share of the group's [start, end) that
+    the chosen piece's segments cover.  A group without a piece (no chain on its period line: none today) gets '', 0, 0, 0, 0."""
+    import numpy as np
+    if not (len(pieces) == len(cons) == len(motifs)) or (len(cons) and (cons["k"] != pieces["k"]).any()):
+        raise ValueError("group_consensus_rows needs the rows phased_consensus returned for these pieces")
+    if len(pieces) and int(pieces["group"].max()) >= len(groups):
+        raise ValueError("group_consensus_rows needs the groups whose chains and links gave these pieces")
+    out = np.zeros(len(groups), dtype=GROUP_CONSENSUS_DTYPE)
+    for name, _ in TANDEM_GROUP_DTYPE:
+        if name in ("copies", "identity") and name not in groups.dtype.names:
+            continue
+        out[name] = groups[name]
+    if "copies" not in groups.dtype.names:
+        plain = tandem_groups(groups, drop_covered=False)
+        out["copies"], out["identity"] = plain["copies"], plain["identity"]
+    best, names = {}, [""] * len(groups)
+    for at, (g, n) in enumerate(zip(pieces["group"].tolist(), pieces["positions"].tolist())):
+        out["pieces"][g] += 1
+        if g not in best or n > best[g][1]:
+            best[g] = (at, n)
+    for g, (at, n) in best.items():
+        span = int(groups["end"][g]) - int(groups["start"][g])
+        names[g] = motifs[at]
+        out["consensus_identity"][g] = int(cons["agree"][at]) / max(n, 1)
+        out["primitive"][g] = primitive_period(motifs[at])
+        out["covered"][g] = n / max(span, 1)
+    return out, names
+
+
 def primitive_period(motif):
     """The smallest divisor d of len(motif) for which the motif is d-periodic (motif == motif[:d] * (len / d))."""
     k = len(motif)
@@ -716,7 +901,7 @@ def consensus_rows(tandem, cons, motifs):
     return out
 
 
-def join_period_chains(chains, links):
+def join_period_chains(chains, links, with_paths=False):
     """The GAPPED tandem repeats of a window: the chains of period_chains (fetched at min_len = 0) joined along the links of
     period_links of the same window, range of k, min_seed and max_gap; join_chains' sibling.  Every chain has at most one link in
     and one out, so the links form paths; one row of PGROUP_DTYPE per path (a chain without links is a path of one), in the order
@@ -727,57 +912,40 @@ def join_period_chains(chains, links):
     min_seed counts 2 d, out to the detour line and back, one of d bases at the repeat's end or between two different periods
     counts d; net_shift: the sum of the shifts (k_last - k_first); gap_cells: the sum of the links' gaps; span_a: the last
     chain's last cell - start + 1; span_b = span_a + k_last - k_first; open: a link into the group's first chain names a
-    predecessor that is not in `chains` (it lies on a line outside the range of k or in front of the window)."""
+    predecessor that is not in `chains` (it lies on a line outside the range of k or in front of the window).  with_paths: returns
+    (rows, paths), the paths as period_paths gives them, for group_segments."""
     import numpy as np
-    n = len(chains)
+    paths, link_out, is_open = _link_paths(chains, links)
     start, length, line = (chains[f].astype(np.int64) for f in ("start", "len", "k"))
-    first = {key: at for at, key in enumerate(zip(start.tolist(), line.tolist()))}
     last_cell = start + length - 1
-    last = {key: at for at, key in enumerate(zip(last_cell.tolist(), line.tolist()))}
-    nxt, link_of, has_in, is_open = [-1] * n, [-1] * n, [False] * n, [False] * n
-    for at, (t_s, t_e, k, s) in enumerate(zip(*(links[f].tolist() for f in ("start", "from_end", "k", "shift")))):
-        y = first.get((t_s, k))
-        if y is None:
-            raise ValueError(f"the link into (start {t_s}, k {k}) names a successor that is not in the list of chains: "
-                             "join_period_chains needs the chains of the same window, range of k, min_seed and max_gap, fetched at min_len = 0")
-        x = last.get((t_e, k - s))
-        if x is None:
-            is_open[y] = True
-        else:
-            nxt[x], link_of[x], has_in[y] = y, at, True
-    out = np.zeros(n - sum(has_in), dtype=PGROUP_DTYPE)
+    out = np.zeros(len(paths), dtype=PGROUP_DTYPE)
     matches, seeds, ks = chains["matches"].tolist(), chains["seeds"].tolist(), line.tolist()
     shift, gap, overlap = (links[f].tolist() for f in ("shift", "gap", "overlap"))
-    at = 0
-    for head in range(n):
-        if has_in[head]:
-            continue
-        g, cur = out[at], head
-        total = n_seeds = n_chains = indel = net = gap_cells = 0
-        k_min = k_max = ks[cur]
+    for at, path in enumerate(paths):
+        g, head, cur = out[at], path[0], path[-1]
+        total = n_seeds = indel = net = gap_cells = 0
+        k_min = k_max = ks[head]
         best = (-1, 0)                                          # (matches, -k) of the chain that names the period
-        while True:
-            total, n_seeds, n_chains = total + matches[cur], n_seeds + seeds[cur], n_chains + 1
-            k_min, k_max, best = min(k_min, ks[cur]), max(k_max, ks[cur]), max(best, (matches[cur], -ks[cur]))
-            if nxt[cur] < 0:
-                break
-            via = link_of[cur]
-            total, indel, net, gap_cells = total - overlap[via], indel + abs(shift[via]), net + shift[via], gap_cells + gap[via]
-            cur = nxt[cur]
+        for c in path:
+            total, n_seeds = total + matches[c], n_seeds + seeds[c]
+            k_min, k_max, best = min(k_min, ks[c]), max(k_max, ks[c]), max(best, (matches[c], -ks[c]))
+            via = link_out[c]
+            if via >= 0:
+                total, indel, net, gap_cells = total - overlap[via], indel + abs(shift[via]), net + shift[via], gap_cells + gap[via]
         g["start"], g["end"], g["open"] = start[head], start[cur] + length[cur] + ks[cur], is_open[head]
         g["k_first"], g["k_min"], g["k_max"], g["period"] = ks[head], k_min, k_max, -best[1]
         g["span_a"] = last_cell[cur] - start[head] + 1
         g["span_b"] = int(g["span_a"]) + ks[cur] - ks[head]
-        g["matches"], g["seeds"], g["chains"], g["indel"], g["net_shift"], g["gap_cells"] = total, n_seeds, n_chains, indel, net, gap_cells
-        at += 1
-    return out
+        g["matches"], g["seeds"], g["chains"], g["indel"], g["net_shift"], g["gap_cells"] = total, n_seeds, len(path), indel, net, gap_cells
+    return (out, paths) if with_paths else out
 
 
-def tandem_groups(groups, drop_covered=True):
+def tandem_groups(groups, drop_covered=True, with_index=False):
     """The repeats of a list of join_period_chains, one row of TANDEM_GROUP_DTYPE each, in the list's order: start, end, period,
     copies = (end - start) / period, identity = matches / max(span_a, span_b), indel, chains, seeds.  A repeat of period 3 is
     also periodic at 6, 9, ... and, with an indel, at neighbouring lines: drop_covered removes a group iff another group of the
-    list with a strictly smaller period covers its [start, end).  Host numpy."""
+    list with a strictly smaller period covers its [start, end).  with_index: returns (rows, the index of every row in
+    `groups`), for group_consensus_rows, whose pieces name groups by that index.  Host numpy."""
     import numpy as np
     out = np.zeros(len(groups), dtype=TANDEM_GROUP_DTYPE)
     for f in ("start", "end", "period", "indel", "chains", "seeds"):
@@ -785,7 +953,7 @@ def tandem_groups(groups, drop_covered=True):
     out["copies"] = (groups["end"] - groups["start"]).astype(np.float64) / np.maximum(groups["period"], 1).astype(np.float64)
     out["identity"] = groups["matches"].astype(np.float64) / np.maximum(np.maximum(groups["span_a"], groups["span_b"]), 1).astype(np.float64)
     if not drop_covered or len(out) < 2:
-        return out
+        return (out, np.arange(len(out))) if with_index else out
     # by start, longest first, smallest period first: a group can only be covered by a group in front of it in this order (or by
     # one with the same interval, which has a smaller period and sorts in front).  Of the groups in front, per period, the
     # largest end is kept; a prefix minimum over the periods answers "does a smaller period reach behind my end".
@@ -797,7 +965,7 @@ def tandem_groups(groups, drop_covered=True):
             keep[at] = False
         if reach.get(p, 0) < b:
             reach[p] = b
-    return out[keep]
+    return (out[keep], np.flatnonzero(keep)) if with_index else out[keep]
 
 
 def tandem_rows(chains, drop_multiples=True):
@@ -1041,6 +1209,15 @@ class Genome:
         result to the repeats."""
         return _period_consensus(self.ctx, (self, contig), begin, end, repeats, counts, with_stats, slice_positions)
 
+    def phased_consensus(self, contig, begin, end, ks, segments, counts=False, with_stats=False, slice_positions=0):
+        """The CONSENSUS MOTIFS of rows whose positions come as SEGMENTS WITH A PHASE, of positions [begin, end) of a contig
+        (prf_phased_consensus): the consensus of a gapped repeat.  ks: one k per row.  segments: any structured array with the
+        fields start, end (relative to begin), row and phase, such as group_segments() returns; position q of a segment lies in
+        column (phase + q - start) mod k of its row.  Segments may come in any order, overlap and interleave; a row without
+        segments is all 'N'.  Returns what period_consensus returns, one row per k.  group_consensus_rows() joins the result to
+        the groups."""
+        return _phased_consensus(self.ctx, (self, contig), begin, end, ks, segments, counts, with_stats, slice_positions)
+
     @property
     def positions(self):
         return self.ctx.lib.prf_genome_positions(self._h)
@@ -1257,6 +1434,10 @@ class Context:
     def period_consensus(self, seq, repeats, begin=0, end=None, counts=False, with_stats=False):
         """Genome.period_consensus for one sequence (str or bytes) in one call: load, count, free (prf_period_consensus_seq)."""
         return _period_consensus(self, seq, begin, end, repeats, counts, with_stats, 0)
+
+    def phased_consensus(self, seq, ks, segments, begin=0, end=None, counts=False, with_stats=False):
+        """Genome.phased_consensus for one sequence (str or bytes) in one call: load, count, free (prf_phased_consensus_seq)."""
+        return _phased_consensus(self, seq, begin, end, ks, segments, counts, with_stats, 0)
 
     def period_links(self, seq, kmin, kmax, min_seed, max_gap, max_shift, n_matches=False, begin=0, end=None, positions=None,
                      with_stats=False):

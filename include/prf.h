@@ -365,6 +365,10 @@ int prf_measure_hbm_read(prf_ctx *ctx, uint64_t bytes, int iters, double *gbps);
  * additions to ABI version 4, declared in prf_consensus.h, which this header includes here; prf_scan_stats.path = 12 is theirs. */
 #include "prf_consensus.h"
 
+/* ---- the consensus motifs of GAPPED repeats: the same columns counted over segments with a phase: three more entry
+ * points, additions to ABI version 4, declared in prf_phased.h, which this header includes here; prf_scan_stats.path = 13 is theirs. */
+#include "prf_phased.h"
+
 #ifdef __cplusplus
 }
 #endif
