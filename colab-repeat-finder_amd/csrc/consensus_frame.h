@@ -1,5 +1,6 @@
 // consensus_frame.h -- the host path that the two consensus products share (consensus_host.cpp: rows (start, end, k), DESIGN 18;
-// phased_host.cpp: segments with a phase; nobody else includes it).  "Rows in, rows out, in the order they came": a
+// phased_host.cpp: segments with a phase; align_host.cpp, DESIGN 20, takes the refusals of the head and of the letters
+// from here and runs on its own; nobody else includes it).  "Rows in, rows out, in the order they came": a
 // small frame of its own on the helpers the matrix and the list products share, not list_run's copy-and-sort.
 //
 // One call: judge the arguments (before the context or the genome is looked at), take the contig's planes, clip `end`, cut the

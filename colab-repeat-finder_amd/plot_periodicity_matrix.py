@@ -18,6 +18,9 @@ between neighbouring period lines), one line per repeat with substitutions and i
 With --group-consensus that list says WHAT each gapped repeat is as well: the consensus motif of its largest piece (the stretch
 over which isolated indels decide the column of every base), counted over segments with a phase:
     plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --groups-tsv vntr.tsv --min-seed 12 --max-gap 8 --max-shift 4 --group-consensus
+With --align on top of either, the list says HOW FAR each repeat is from its motif: substitutions, insertions and deletions of
+the best alignment of the whole repeat to the endless repetition of the motif, the aligned identity and the aligned copies:
+    plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --groups-tsv vntr.tsv --min-seed 12 --max-gap 8 --max-shift 4 --group-consensus --align
 """
 import argparse
 import os
@@ -73,6 +76,12 @@ def build_parser():
                                                                   "that the chosen piece covers.")
     p.add_argument("--min-group-consensus-identity", type=float, help="With --group-consensus: keep repeats of at least this "
                                                                       "identity against their consensus motif.")
+    p.add_argument("--align", action="store_true", help="With --consensus or --group-consensus: append six columns per repeat: "
+                   "edits, substitutions, insertions and deletions of the best alignment of the repeat to the endless repetition of "
+                   "its consensus motif (unit costs, free at both ends of the motif), the aligned identity (matches / (positions + "
+                   "deletions)) and the aligned copies (motif letters the alignment runs over / period).  A '.' in all six: a "
+                   "repeat above a limit of one alignment.")
+    p.add_argument("--min-aligned-identity", type=float, help="With --align: keep repeats of at least this aligned identity.")
     return p
 
 
@@ -95,6 +104,13 @@ def check_chain_args(args, parser):
             parser.error("--min-group-consensus-identity belongs to --group-consensus")
         if not 0.0 <= args.min_group_consensus_identity <= 1.0:
             parser.error(f"--min-group-consensus-identity is set to {args.min_group_consensus_identity}. It must be 0 .. 1.")
+    if args.align and not (args.consensus or args.group_consensus):
+        parser.error("--align needs the motifs of --consensus (with --chains-tsv) or --group-consensus (with --groups-tsv)")
+    if args.min_aligned_identity is not None:
+        if not args.align:
+            parser.error("--min-aligned-identity belongs to --align")
+        if not 0.0 <= args.min_aligned_identity <= 1.0:
+            parser.error(f"--min-aligned-identity is set to {args.min_aligned_identity}. It must be 0 .. 1.")
     if not args.groups_tsv:
         if args.max_shift is not None:
             parser.error("--max-shift belongs to --groups-tsv")
@@ -222,6 +238,41 @@ def consensus_columns(rows, motifs):
         yield f"\t{motif}\t{identity:.4f}\t{primitive}\t{prf_native.canonical_motif(motif)}\n"
 
 
+def aligned_of(genome, begin, end, rows, motifs):
+    """(rows of prf_native.alignment_rows, which of them were aligned) of rows with the fields start, end and k or period against
+    one motif each: every row within the limits of one alignment (and with a motif), sent in batches that respect the limits of
+    one call; the others stay 0."""
+    import numpy as np
+    import prf_native
+    table = np.zeros(len(rows), dtype=prf_native.REPEAT_DTYPE)
+    table["start"], table["end"], table["k"] = rows["start"], rows["end"], [len(m) for m in motifs]
+    fits = (table["k"] >= 1) & (table["k"] <= prf_native.ALIGN_MAX_K) & (table["end"] - table["start"] <= prf_native.ALIGN_MAX_LEN)
+    sent = np.flatnonzero(fits)
+    parts = [np.zeros(0, dtype=prf_native.ALIGNMENT_DTYPE)]
+    for a, b in consensus_batches(table["k"][sent].tolist(), prf_native.CONSENSUS_MAX_ROWS, prf_native.CONSENSUS_MAX_LETTERS):
+        parts.append(genome.motif_align(0, begin, end, table[sent[a:b]], [motifs[at] for at in sent[a:b].tolist()]))
+    got = np.zeros(len(rows), dtype=prf_native.ALIGNMENT_DTYPE)
+    got["consumed"] = table["end"] - table["start"]             # a row that was not sent: no edits, and never shown
+    got[sent] = np.concatenate(parts)
+    return prf_native.alignment_rows(rows, got), fits
+
+
+def align_columns(rows, fits):
+    """The six columns --align appends to a line, per row of prf_native.alignment_rows."""
+    for ok, edits, subs, ins, dele, identity, copies in zip(fits.tolist(), *(rows[f].tolist() for f in (
+            "edits", "subs", "ins", "del", "aligned_identity", "aligned_copies"))):
+        yield f"\t{edits}\t{subs}\t{ins}\t{dele}\t{identity:.4f}\t{copies:.2f}\n" if ok else "\t.\t.\t.\t.\t.\t.\n"
+
+
+def with_alignments(args, lines, aligned, fits):
+    """The lines with the columns of --align, without those --min-aligned-identity drops (a row above a limit among them)."""
+    lines = [line[:-1] + more for line, more in zip(lines, align_columns(aligned, fits))]
+    if args.min_aligned_identity is not None:
+        keep = (fits & (aligned["aligned_identity"] >= args.min_aligned_identity)).tolist()
+        lines = [line for line, kept in zip(lines, keep) if kept]
+    return lines
+
+
 def list_chains(args, chrom, seq, begin, end, context=None):
     """--chains-tsv: the interval in windows of --chain-window start positions, the lists concatenated; with --consensus the
     consensus of every repeat that is left, from the same resident genome."""
@@ -238,6 +289,8 @@ def list_chains(args, chrom, seq, begin, end, context=None):
         rows = rows[rows["identity"] >= args.min_identity]
         if args.consensus:
             named, motifs = consensus_of(genome, begin, end, rows)
+            if args.align:
+                aligned, fits = aligned_of(genome, begin, end, rows, motifs)
     finally:
         genome.free()
     lines = list(chain_lines(chrom, begin, seq, rows))
@@ -246,6 +299,10 @@ def list_chains(args, chrom, seq, begin, end, context=None):
         if args.min_consensus_identity is not None:
             keep = (named["consensus_identity"] >= args.min_consensus_identity).tolist()
             lines = [line for line, kept in zip(lines, keep) if kept]
+            if args.align:
+                aligned, fits = aligned[np.array(keep, dtype=bool)], fits[np.array(keep, dtype=bool)]
+        if args.align:
+            lines = with_alignments(args, lines, aligned, fits)
     with open(args.chains_tsv, "wt") as out:
         out.writelines(lines)
     print(f"Wrote {args.chains_tsv}: {len(lines)} repeats")
@@ -332,6 +389,8 @@ def list_groups(args, chrom, seq, begin, end, context=None):
             keep[kept] = True
             named, motifs = group_consensus_of(genome, begin, end, joined, keep, chains, links)
             named, motifs = named[kept], [motifs[at] for at in kept.tolist()]
+            if args.align:                                      # the whole [start, end) of a group against the motif of its chosen piece
+                aligned, fits = aligned_of(genome, begin, end, rows, motifs)
     finally:
         genome.free()
     lines = list(group_lines(chrom, begin, seq, rows))
@@ -340,6 +399,10 @@ def list_groups(args, chrom, seq, begin, end, context=None):
         if args.min_group_consensus_identity is not None:
             passed = (named["consensus_identity"] >= args.min_group_consensus_identity).tolist()
             lines = [line for line, ok in zip(lines, passed) if ok]
+            if args.align:
+                aligned, fits = aligned[np.array(passed, dtype=bool)], fits[np.array(passed, dtype=bool)]
+        if args.align:
+            lines = with_alignments(args, lines, aligned, fits)
     with open(args.groups_tsv, "wt") as out:
         out.writelines(lines)
     print(f"Wrote {args.groups_tsv}: {len(lines)} repeats")

@@ -189,6 +189,15 @@ PHASED_MAX_SEGMENTS = 1 << 24        # PRF_PHASED_MAX_SEGMENTS
 PIECE_DTYPE = [("group", "<u8"), ("anchor", "<u8"), ("end", "<u8"), ("k", "<u4"), ("segments", "<u4"), ("positions", "<u8")]
 # one row of group_consensus_rows per gapped repeat: TANDEM_GROUP_DTYPE and what the consensus of its largest piece adds
 GROUP_CONSENSUS_DTYPE = TANDEM_GROUP_DTYPE + [("consensus_identity", "<f8"), ("primitive", "<u4"), ("pieces", "<u4"), ("covered", "<f8")]
+# the entry points of the alignment of repeats to their motifs (include/prf_align.h, which prf.h includes)
+ALIGN_EXPORTS = ["prf_motif_align", "prf_motif_align_seq"]
+ALIGNMENT_DTYPE = [("edits", "<u4"), ("indels", "<u4"), ("consumed", "<u4"), ("start_column", "<u4"), ("end_column", "<u4"),
+                   ("reserved", "<u4")]                                                                       # prf_alignment, 24 bytes
+ALIGN_MAX_K = 1024                   # PRF_ALIGN_MAX_K
+ALIGN_MAX_LEN = 1 << 19              # PRF_ALIGN_MAX_LEN: positions per repeat
+# what alignment_rows appends to its rows
+ALIGNED_FIELDS = [("edits", "<u4"), ("subs", "<u4"), ("ins", "<u4"), ("del", "<u4"), ("aligned_matches", "<u4"),
+                  ("aligned_identity", "<f8"), ("aligned_copies", "<f8")]
 DIRECTIONS = {"main": 1, "anti": 2, "both": 3}
 DOT_LAUNCH_CELLS = 1 << 36   # PRF_DOT_LAUNCH_CELLS
 DOT_MAX_CELLS = 1 << 42      # PRF_DOT_MAX_CELLS
@@ -332,6 +341,10 @@ def load_library():
         lib.prf_phased_consensus.argtypes = [vp, vp, ctypes.c_uint32] + phased_tail
         lib.prf_phased_consensus_ex.argtypes = [vp, vp, ctypes.c_uint32] + phased_tail + [ctypes.c_uint64]
         lib.prf_phased_consensus_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + phased_tail
+        # begin, end, rows, n_rows, motifs, letters_length, dst, stats
+        align_tail = [ctypes.c_uint64] * 2 + [vp, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64, vp, ctypes.POINTER(ScanStats)]
+        lib.prf_motif_align.argtypes = [vp, vp, ctypes.c_uint32] + align_tail
+        lib.prf_motif_align_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + align_tail
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
         lib.prf_measure_hbm_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -641,9 +654,10 @@ def _period_links(ctx, target, begin, end, kmin, kmax, min_seed, max_gap, max_sh
                       "min_seed, fewer periods or fewer positions", with_stats)
 
 
-def _period_consensus(ctx, target, begin, end, repeats, counts, with_stats, slice_positions):
-    """The period_consensus calls.  target: (genome, contig) or one sequence.  Returns (rows of CONSENSUS_DTYPE, list of str), then
-    the counts as an array of (sum of k, 4) if asked, then the ScanStats with_stats."""
+def _repeat_table(target, begin, end, repeats, slice_positions=0):
+    """The argument checks that the calls over repeats (start, end, k) share.  Returns (what the library is given in front of the
+    range, `end` as the library takes it, what must stay alive during the call, the rows as REPEAT_DTYPE, their number, the sum of
+    k)."""
     import numpy as np
     try:
         start, stop, k = (np.asarray(repeats[name]) for name in ("start", "end", "k"))
@@ -667,6 +681,14 @@ def _period_consensus(ctx, target, begin, end, repeats, counts, with_stats, slic
         letters = int(rows["k"][:n_rows].sum(dtype=np.uint64))
         if letters > CONSENSUS_MAX_LETTERS:
             raise ValueError(f"the k of the repeats add up to {letters}, more than one call takes ({CONSENSUS_MAX_LETTERS}): send them in batches")
+    return where, c_end, keep, rows, n_rows, letters
+
+
+def _period_consensus(ctx, target, begin, end, repeats, counts, with_stats, slice_positions):
+    """The period_consensus calls.  target: (genome, contig) or one sequence.  Returns (rows of CONSENSUS_DTYPE, list of str), then
+    the counts as an array of (sum of k, 4) if asked, then the ScanStats with_stats."""
+    import numpy as np
+    where, c_end, keep, rows, n_rows, letters = _repeat_table(target, begin, end, repeats, slice_positions)
     out = np.zeros(max(1, n_rows), dtype=CONSENSUS_DTYPE)
     motifs = np.zeros(max(1, letters), dtype=np.uint8)
     table = np.zeros((max(1, letters), 4), dtype=np.uint32) if counts else None
@@ -745,6 +767,79 @@ def _phased_consensus(ctx, target, begin, end, ks, segments, counts, with_stats,
     if counts:
         result += (sums[:letters],)
     return result + (stats,) if with_stats else result
+
+
+def _motif_letters(motifs, ks):
+    """The motifs of rows of these k as one buffer of letters: a list of str, one per row, or the letters (str or bytes) that a
+    consensus call returned, which are checked for their length only -- the library names a letter it does not take."""
+    if isinstance(motifs, (str, bytes, bytearray)):
+        text = motifs.encode("ascii", "replace") if isinstance(motifs, str) else bytes(motifs)
+        if len(text) != sum(ks):
+            raise ValueError(f"the motifs hold {len(text)} letters, the k of the repeats add up to {sum(ks)}")
+        return text
+    try:
+        parts = list(motifs)
+    except TypeError:
+        parts = [None]
+    if not all(isinstance(m, (str, bytes, bytearray)) for m in parts):
+        raise ValueError("motifs must be a list of str, one per repeat, or the letters a consensus call returned")
+    parts = [m.encode("ascii", "replace") if isinstance(m, str) else bytes(m) for m in parts]
+    if len(parts) != len(ks):
+        raise ValueError(f"{len(parts)} motifs for {len(ks)} repeats")
+    for at, (m, k) in enumerate(zip(parts, ks)):
+        if len(m) != k:
+            raise ValueError(f"repeat {at}: the motif has {len(m)} letters, k is {k}")
+    return b"".join(parts)
+
+
+def _motif_align(ctx, target, begin, end, repeats, motifs, with_stats):
+    """The motif_align calls.  target: (genome, contig) or one sequence.  Returns the rows of ALIGNMENT_DTYPE, then the ScanStats
+    with_stats."""
+    import numpy as np
+    where, c_end, keep, rows, n_rows, letters = _repeat_table(target, begin, end, repeats)
+    if n_rows:
+        k, length = rows["k"][:n_rows], rows["end"][:n_rows] - rows["start"][:n_rows]
+        if (k > ALIGN_MAX_K).any():
+            at = int(np.argmax(k > ALIGN_MAX_K))
+            raise ValueError(f"repeat {at}: k = {k[at]} is more than an alignment takes ({ALIGN_MAX_K})")
+        if (length > ALIGN_MAX_LEN).any():
+            at = int(np.argmax(length > ALIGN_MAX_LEN))
+            raise ValueError(f"repeat {at}: {length[at]} positions are more than an alignment takes ({ALIGN_MAX_LEN})")
+    text = _motif_letters(motifs, rows["k"][:n_rows].tolist())
+    out = np.zeros(max(1, n_rows), dtype=ALIGNMENT_DTYPE)
+    stats = ScanStats()
+    if keep is not None:
+        fn, head = ctx.lib.prf_motif_align_seq, (ctx._h,)
+    else:
+        fn, head = ctx.lib.prf_motif_align, (ctx._h, target[0]._h)
+    _check(ctx.lib, fn(*head, *where, begin, c_end, rows.ctypes.data, n_rows, text, len(text), out.ctypes.data, ctypes.byref(stats)))
+    got = out[:n_rows].copy()
+    return (got, stats) if with_stats else got
+
+
+def alignment_rows(rows, align):
+    """Rows with the fields start, end and k -- or period, as the rows of tandem_groups() and group_consensus_rows() call it --
+    with what motif_align says of them, in their order: the fields of `rows`, then ALIGNED_FIELDS: edits, subs = edits - indels,
+    ins = (indels + n - consumed) / 2, del = (indels - n + consumed) / 2, aligned_matches = n - subs - ins (the rows of
+    tandem_rows() have a `matches` of their own: the chain's), aligned_identity = aligned_matches / (n + del) and aligned_copies =
+    consumed / k, with n = end - start.  Host numpy."""
+    import numpy as np
+    k_field = "k" if "k" in rows.dtype.names else "period"
+    if len(rows) != len(align):
+        raise ValueError("alignment_rows needs the rows motif_align returned for these repeats")
+    out = np.zeros(len(rows), dtype=rows.dtype.descr + ALIGNED_FIELDS)
+    for name in rows.dtype.names:
+        out[name] = rows[name]
+    n = (rows["end"].astype(np.int64) - rows["start"].astype(np.int64))
+    edits, indels, consumed = (align[f].astype(np.int64) for f in ("edits", "indels", "consumed"))
+    if len(rows) and (((indels + n - consumed) % 2 != 0).any() or (consumed > n + indels).any() or (n > consumed + indels).any()):
+        raise ValueError("alignment_rows needs the rows motif_align returned for these repeats")
+    out["edits"], out["subs"] = edits, edits - indels
+    out["ins"], out["del"] = (indels + n - consumed) // 2, (indels - n + consumed) // 2
+    out["aligned_matches"] = n - out["subs"] - out["ins"]
+    out["aligned_identity"] = out["aligned_matches"] / np.maximum(n + out["del"], 1)
+    out["aligned_copies"] = consumed / np.maximum(rows[k_field].astype(np.int64), 1)
+    return out
 
 
 def _link_paths(chains, links):
@@ -1218,6 +1313,16 @@ class Genome:
         the groups."""
         return _phased_consensus(self.ctx, (self, contig), begin, end, ks, segments, counts, with_stats, slice_positions)
 
+    def motif_align(self, contig, begin, end, repeats, motifs, with_stats=False):
+        """The ALIGNMENT of repeats of positions [begin, end) of a contig to their motifs (prf_motif_align): each repeat's
+        positions against the endless repetition of its motif, free at both ends of the motif, unit costs.  repeats: any
+        structured array with the fields start, end (relative to begin) and k <= ALIGN_MAX_K, of at most ALIGN_MAX_LEN positions
+        each.  motifs: a list of str over A C G T N, one of k letters per repeat, or the letters a consensus call returned, in
+        one str or bytes.  Returns a numpy structured array in the order of the repeats with the fields edits (substitutions +
+        insertions + deletions, the least possible), indels (the least among those), consumed (motif letters the alignment runs
+        over, the least among those), start_column and end_column.  alignment_rows() derives the rest."""
+        return _motif_align(self.ctx, (self, contig), begin, end, repeats, motifs, with_stats)
+
     @property
     def positions(self):
         return self.ctx.lib.prf_genome_positions(self._h)
@@ -1438,6 +1543,10 @@ class Context:
     def phased_consensus(self, seq, ks, segments, begin=0, end=None, counts=False, with_stats=False):
         """Genome.phased_consensus for one sequence (str or bytes) in one call: load, count, free (prf_phased_consensus_seq)."""
         return _phased_consensus(self, seq, begin, end, ks, segments, counts, with_stats, 0)
+
+    def motif_align(self, seq, repeats, motifs, begin=0, end=None, with_stats=False):
+        """Genome.motif_align for one sequence (str or bytes) in one call: load, align, free (prf_motif_align_seq)."""
+        return _motif_align(self, seq, begin, end, repeats, motifs, with_stats)
 
     def period_links(self, seq, kmin, kmax, min_seed, max_gap, max_shift, n_matches=False, begin=0, end=None, positions=None,
                      with_stats=False):

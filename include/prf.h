@@ -369,6 +369,11 @@ int prf_measure_hbm_read(prf_ctx *ctx, uint64_t bytes, int iters, double *gbps);
  * points, additions to ABI version 4, declared in prf_phased.h, which this header includes here; prf_scan_stats.path = 13 is theirs. */
 #include "prf_phased.h"
 
+/* ---- the alignment of such repeats to their motifs: substitutions, insertions and deletions against the endless repetition of
+ * the motif: two more entry points, additions to ABI version 4, declared in prf_align.h, which this header includes
+ * here; prf_scan_stats.path = 14 is theirs. */
+#include "prf_align.h"
+
 #ifdef __cplusplus
 }
 #endif
