@@ -21,6 +21,9 @@ over which isolated indels decide the column of every base), counted over segmen
 With --align on top of either, the list says HOW FAR each repeat is from its motif: substitutions, insertions and deletions of
 the best alignment of the whole repeat to the endless repetition of the motif, the aligned identity and the aligned copies:
     plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --groups-tsv vntr.tsv --min-seed 12 --max-gap 8 --max-shift 4 --group-consensus --align
+--align-path adds the alignment itself as a CIGAR, --refine R re-estimates each motif from its aligned copies and aligns again,
+--copies-tsv lists where each copy begins and ends and what it differs in:
+    plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --groups-tsv vntr.tsv --min-seed 12 --max-gap 8 --max-shift 4 --group-consensus --align --align-path --refine 2 --copies-tsv copies.tsv
 """
 import argparse
 import os
@@ -82,6 +85,14 @@ def build_parser():
                    "deletions)) and the aligned copies (motif letters the alignment runs over / period).  A '.' in all six: a "
                    "repeat above a limit of one alignment.")
     p.add_argument("--min-aligned-identity", type=float, help="With --align: keep repeats of at least this aligned identity.")
+    p.add_argument("--align-path", action="store_true", help="With --align: append a column `cigar`: the alignment itself as run "
+                   "lengths of = (match), X (substitution), I (inserted base) and D (deleted motif letter).")
+    p.add_argument("--refine", type=int, default=0, metavar="R", help="With --align: re-estimate every motif from its aligned "
+                   "copies and align again, R rounds at most; the reported motif, its canonical form and the columns of --align are "
+                   "those of the last round, and a column `refined` says in how many rounds the motif changed.")
+    p.add_argument("--copies-tsv", help="With --align: also write one line per aligned copy of every listed repeat: chrom, start, "
+                                        "end and period of the repeat, the copy's number, start and end, its substitutions, "
+                                        "insertions and deletions.")
     return p
 
 
@@ -111,6 +122,12 @@ def check_chain_args(args, parser):
             parser.error("--min-aligned-identity belongs to --align")
         if not 0.0 <= args.min_aligned_identity <= 1.0:
             parser.error(f"--min-aligned-identity is set to {args.min_aligned_identity}. It must be 0 .. 1.")
+    if not args.align:
+        for name in ("align_path", "refine", "copies_tsv"):
+            if getattr(args, name):
+                parser.error(f"--{name.replace('_', '-')} belongs to --align")
+    if not 0 <= args.refine <= 100:
+        parser.error(f"--refine is set to {args.refine}. It must be 0 .. 100.")
     if not args.groups_tsv:
         if args.max_shift is not None:
             parser.error("--max-shift belongs to --groups-tsv")
@@ -264,13 +281,83 @@ def align_columns(rows, fits):
         yield f"\t{edits}\t{subs}\t{ins}\t{dele}\t{identity:.4f}\t{copies:.2f}\n" if ok else "\t.\t.\t.\t.\t.\t.\n"
 
 
-def with_alignments(args, lines, aligned, fits):
-    """The lines with the columns of --align, without those --min-aligned-identity drops (a row above a limit among them)."""
+def with_alignments(args, lines, aligned, fits, detail=None):
+    """The lines with the columns of --align (and, from `detail`, of --align-path and --refine), without those
+    --min-aligned-identity drops (a row above a limit among them)."""
     lines = [line[:-1] + more for line, more in zip(lines, align_columns(aligned, fits))]
+    if detail is not None:
+        lines = [line[:-1] + more for line, more in zip(lines, path_columns(args, detail, fits))]
     if args.min_aligned_identity is not None:
         keep = (fits & (aligned["aligned_identity"] >= args.min_aligned_identity)).tolist()
         lines = [line for line, kept in zip(lines, keep) if kept]
     return lines
+
+
+def wants_paths(args):
+    return bool(args.align_path or args.refine or args.copies_tsv)
+
+
+def aligned_paths_of(genome, begin, end, rows, motifs, rounds):
+    """aligned_of with the paths (--align-path, --refine, --copies-tsv): (rows of prf_native.alignment_rows, which of them were
+    aligned, detail) with detail = the motifs of the last round, per row the rounds of --refine that changed its motif, and the
+    row's path (None: not aligned).  Batches respect the limits of one call, the positions of one call's path among them."""
+    import numpy as np
+    import prf_native
+    table = np.zeros(len(rows), dtype=prf_native.REPEAT_DTYPE)
+    table["start"], table["end"], table["k"] = rows["start"], rows["end"], [len(m) for m in motifs]
+    fits = (table["k"] >= 1) & (table["k"] <= prf_native.ALIGN_MAX_K) & (table["end"] - table["start"] <= prf_native.ALIGN_MAX_LEN)
+    sent = np.flatnonzero(fits)
+    got = np.zeros(len(rows), dtype=prf_native.ALIGNMENT_DTYPE)
+    got["consumed"] = table["end"] - table["start"]             # a row that was not sent: no edits, and never shown
+    detail = {"motifs": list(motifs), "refined": np.zeros(len(rows), dtype=np.uint32), "paths": [None] * len(rows),
+              "k": table["k"].tolist(), "start": table["start"].tolist()}
+    lengths = (table["end"] - table["start"])[sent].tolist()
+    for a, b in piece_batches(table["k"][sent].tolist(), lengths, prf_native.CONSENSUS_MAX_ROWS, prf_native.CONSENSUS_MAX_LETTERS,
+                              prf_native.ALIGNPATH_MAX_POSITIONS):
+        which = sent[a:b]
+        part, names = table[which], [motifs[at] for at in which.tolist()]
+        if rounds:
+            names, _, changed = prf_native.refine_motifs(genome, 0, begin, end, part, names, rounds)
+            detail["refined"][which] = changed
+        got[which], paths = genome.motif_align_path(0, begin, end, part, names)
+        for at, name, path in zip(which.tolist(), names, paths):
+            detail["motifs"][at], detail["paths"][at] = name, path
+    return prf_native.alignment_rows(rows, got), fits, detail
+
+
+def take_detail(detail, keep):
+    """The detail of the rows whose `keep` is set."""
+    import numpy as np
+    keep = np.asarray(keep, dtype=bool)
+    return {name: (value[keep] if isinstance(value, np.ndarray) else [v for v, kept in zip(value, keep.tolist()) if kept])
+            for name, value in detail.items()}
+
+
+def path_columns(args, detail, fits):
+    """The columns --align-path (cigar) and --refine (refined) append to a line; '.' for a row above a limit."""
+    import prf_native
+    for ok, path, k, refined in zip(fits.tolist(), detail["paths"], detail["k"], detail["refined"].tolist()):
+        more = ""
+        if args.align_path:
+            more += "\t" + (prf_native.path_cigar(path, k) if ok else ".")
+        if args.refine:
+            more += f"\t{refined}" if ok else "\t."
+        yield more + "\n"
+
+
+def write_copies(args, chrom, begin, aligned, fits, detail):
+    """--copies-tsv: one line per aligned copy of the rows that are listed."""
+    import prf_native
+    keep = fits if args.min_aligned_identity is None else fits & (aligned["aligned_identity"] >= args.min_aligned_identity)
+    n_lines = 0
+    with open(args.copies_tsv, "wt") as out:
+        for ok, path, k, start, end in zip(keep.tolist(), detail["paths"], detail["k"], detail["start"], aligned["end"].tolist()):
+            if not ok:
+                continue
+            for copy, first, last, subs, ins, dels in prf_native.path_copies(path, start, k).tolist():
+                out.write(f"{chrom}\t{begin + start}\t{begin + end}\t{k}\t{copy}\t{begin + first}\t{begin + last}\t{subs}\t{ins}\t{dels}\n")
+                n_lines += 1
+    print(f"Wrote {args.copies_tsv}: {n_lines} copies")
 
 
 def list_chains(args, chrom, seq, begin, end, context=None):
@@ -289,7 +376,11 @@ def list_chains(args, chrom, seq, begin, end, context=None):
         rows = rows[rows["identity"] >= args.min_identity]
         if args.consensus:
             named, motifs = consensus_of(genome, begin, end, rows)
-            if args.align:
+            detail = None
+            if args.align and wants_paths(args):
+                aligned, fits, detail = aligned_paths_of(genome, begin, end, rows, motifs, args.refine)
+                motifs = detail["motifs"]                           # of the last round of --refine
+            elif args.align:
                 aligned, fits = aligned_of(genome, begin, end, rows, motifs)
     finally:
         genome.free()
@@ -301,8 +392,11 @@ def list_chains(args, chrom, seq, begin, end, context=None):
             lines = [line for line, kept in zip(lines, keep) if kept]
             if args.align:
                 aligned, fits = aligned[np.array(keep, dtype=bool)], fits[np.array(keep, dtype=bool)]
+                detail = take_detail(detail, keep) if detail is not None else None
         if args.align:
-            lines = with_alignments(args, lines, aligned, fits)
+            lines = with_alignments(args, lines, aligned, fits, detail)
+            if args.copies_tsv:
+                write_copies(args, chrom, begin, aligned, fits, detail)
     with open(args.chains_tsv, "wt") as out:
         out.writelines(lines)
     print(f"Wrote {args.chains_tsv}: {len(lines)} repeats")
@@ -389,7 +483,11 @@ def list_groups(args, chrom, seq, begin, end, context=None):
             keep[kept] = True
             named, motifs = group_consensus_of(genome, begin, end, joined, keep, chains, links)
             named, motifs = named[kept], [motifs[at] for at in kept.tolist()]
-            if args.align:                                      # the whole [start, end) of a group against the motif of its chosen piece
+            detail = None
+            if args.align and wants_paths(args):                # the whole [start, end) of a group against the motif of its chosen piece
+                aligned, fits, detail = aligned_paths_of(genome, begin, end, rows, motifs, args.refine)
+                motifs = detail["motifs"]                           # of the last round of --refine
+            elif args.align:
                 aligned, fits = aligned_of(genome, begin, end, rows, motifs)
     finally:
         genome.free()
@@ -401,8 +499,11 @@ def list_groups(args, chrom, seq, begin, end, context=None):
             lines = [line for line, ok in zip(lines, passed) if ok]
             if args.align:
                 aligned, fits = aligned[np.array(passed, dtype=bool)], fits[np.array(passed, dtype=bool)]
+                detail = take_detail(detail, passed) if detail is not None else None
         if args.align:
-            lines = with_alignments(args, lines, aligned, fits)
+            lines = with_alignments(args, lines, aligned, fits, detail)
+            if args.copies_tsv:
+                write_copies(args, chrom, begin, aligned, fits, detail)
     with open(args.groups_tsv, "wt") as out:
         out.writelines(lines)
     print(f"Wrote {args.groups_tsv}: {len(lines)} repeats")

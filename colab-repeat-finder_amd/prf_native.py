@@ -198,6 +198,14 @@ ALIGN_MAX_LEN = 1 << 19              # PRF_ALIGN_MAX_LEN: positions per repeat
 # what alignment_rows appends to its rows
 ALIGNED_FIELDS = [("edits", "<u4"), ("subs", "<u4"), ("ins", "<u4"), ("del", "<u4"), ("aligned_matches", "<u4"),
                   ("aligned_identity", "<f8"), ("aligned_copies", "<f8")]
+# the entry points of the alignment with its path (include/prf_alignpath.h, which prf.h includes)
+ALIGNPATH_EXPORTS = ["prf_motif_align_path", "prf_motif_align_path_ex", "prf_motif_align_path_seq"]
+ALIGNPATH_MAX_POSITIONS = 1 << 30    # PRF_ALIGNPATH_MAX_POSITIONS: entries of one call's path
+PATH_INS = 0x8000                    # PRF_PATH_INS: the position is an insertion behind the entry's column
+PATH_SUB = 0x4000                    # PRF_PATH_SUB: the position is aligned to the entry's column and does not match it
+PATH_COLUMN = 0x03FF                 # PRF_PATH_COLUMN
+# what path_copies returns per copy
+PATH_COPY_DTYPE = [("copy", "<u4"), ("start", "<u8"), ("end", "<u8"), ("subs", "<u4"), ("ins", "<u4"), ("dels", "<u4")]
 DIRECTIONS = {"main": 1, "anti": 2, "both": 3}
 DOT_LAUNCH_CELLS = 1 << 36   # PRF_DOT_LAUNCH_CELLS
 DOT_MAX_CELLS = 1 << 42      # PRF_DOT_MAX_CELLS
@@ -345,6 +353,10 @@ def load_library():
         align_tail = [ctypes.c_uint64] * 2 + [vp, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64, vp, ctypes.POINTER(ScanStats)]
         lib.prf_motif_align.argtypes = [vp, vp, ctypes.c_uint32] + align_tail
         lib.prf_motif_align_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + align_tail
+        path_tail = align_tail[:-1] + [vp, ctypes.c_uint64, vp, ctypes.POINTER(ScanStats)]
+        lib.prf_motif_align_path.argtypes = [vp, vp, ctypes.c_uint32] + path_tail
+        lib.prf_motif_align_path_ex.argtypes = [vp, vp, ctypes.c_uint32] + path_tail + [ctypes.c_uint64]
+        lib.prf_motif_align_path_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + path_tail
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
         lib.prf_measure_hbm_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -842,6 +854,164 @@ def alignment_rows(rows, align):
     return out
 
 
+def _motif_align_path(ctx, target, begin, end, repeats, motifs, with_counts, with_stats, trace_bytes):
+    """The motif_align_path calls.  target: (genome, contig) or one sequence.  Returns (rows of ALIGNMENT_DTYPE, the paths: one
+    uint16 array per repeat, views of one buffer), then the counts as an array of (sum of k, 6) with_counts, then the ScanStats
+    with_stats."""
+    import numpy as np
+    where, c_end, keep, rows, n_rows, letters = _repeat_table(target, begin, end, repeats)
+    _int_check("trace_bytes", trace_bytes, 0)
+    length = rows["end"][:n_rows] - rows["start"][:n_rows]
+    if n_rows:
+        k = rows["k"][:n_rows]
+        if (k > ALIGN_MAX_K).any():
+            at = int(np.argmax(k > ALIGN_MAX_K))
+            raise ValueError(f"repeat {at}: k = {k[at]} is more than an alignment takes ({ALIGN_MAX_K})")
+        if (length > ALIGN_MAX_LEN).any():
+            at = int(np.argmax(length > ALIGN_MAX_LEN))
+            raise ValueError(f"repeat {at}: {length[at]} positions are more than an alignment takes ({ALIGN_MAX_LEN})")
+    positions = int(length.sum(dtype=np.uint64))
+    if positions > ALIGNPATH_MAX_POSITIONS:
+        raise ValueError(f"the repeats add up to {positions} positions, more than one call's path takes ({ALIGNPATH_MAX_POSITIONS}): send them in batches")
+    text = _motif_letters(motifs, rows["k"][:n_rows].tolist())
+    out = np.zeros(max(1, n_rows), dtype=ALIGNMENT_DTYPE)
+    path = np.zeros(max(1, positions), dtype=np.uint16)
+    table = np.zeros((max(1, letters), 6), dtype=np.uint32) if with_counts else None
+    stats = ScanStats()
+    tail = (begin, c_end, rows.ctypes.data, n_rows, text, len(text), out.ctypes.data, path.ctypes.data, positions,
+            table.ctypes.data if with_counts else None, ctypes.byref(stats))
+    if keep is not None:
+        if trace_bytes:
+            raise ValueError("trace_bytes belongs to a resident genome: the one-shot form has no such knob")
+        rc = ctx.lib.prf_motif_align_path_seq(ctx._h, *where, *tail)
+    else:
+        rc = ctx.lib.prf_motif_align_path_ex(ctx._h, target[0]._h, *where, *tail, trace_bytes)
+    _check(ctx.lib, rc)
+    firsts = np.concatenate([[0], np.cumsum(length, dtype=np.uint64)]).astype(np.int64).tolist()
+    result = (out[:n_rows].copy(), [path[firsts[at]:firsts[at + 1]] for at in range(n_rows)])
+    if with_counts:
+        result += (table[:letters],)
+    return result + (stats,) if with_stats else result
+
+
+def path_deletions(path_row, k):
+    """Per position i of a row's path but the last, the number of deleted motif letters between i and i + 1, from the path alone:
+    with state = path[i] & PATH_COLUMN, (c - 1 - state) mod k if i + 1 is aligned at column c, (c - state) mod k if it is an
+    insertion with column c.  Host numpy."""
+    import numpy as np
+    p = np.asarray(path_row).astype(np.int64)
+    state, col, ins = p[:-1] & PATH_COLUMN, p[1:] & PATH_COLUMN, (p[1:] & PATH_INS) != 0
+    return np.where(ins, col - state, col - 1 - state) % int(k)
+
+
+def path_cigar(path_row, k):
+    """The CIGAR of a row's path: run lengths of = (match), X (substitution), I (insertion: a position against nothing) and
+    D (deletion: motif letters against nothing, path_deletions), in the order of the positions.  Host numpy."""
+    import numpy as np
+    p = np.asarray(path_row).astype(np.int64)
+    if not len(p):
+        return ""
+    ops = np.where(p & PATH_INS, ord("I"), np.where(p & PATH_SUB, ord("X"), ord("="))).astype(np.uint8)
+    dels = np.concatenate([path_deletions(p, k), [0]])
+    out, run_op, run = [], None, 0
+    for op, d in zip(ops.tobytes().decode(), dels.tolist()):
+        if op == run_op:
+            run += 1
+        else:
+            if run:
+                out.append(f"{run}{run_op}")
+            run_op, run = op, 1
+        if d:
+            out.append(f"{run}{run_op}{d}D")
+            run_op, run = None, 0
+    if run:
+        out.append(f"{run}{run_op}")
+    return "".join(out)
+
+
+def aligned_consensus(counts, motifs):
+    """The motifs re-estimated from the aligned columns: per column the letter with the most aligned positions (counts[:, 0:4] of
+    motif_align_path), ties in the order A, C, G, T; a column without any keeps its letter.  motifs: a list of str, or the letters
+    in one str or bytes; the result has the same form (bytes come back as str).  Host numpy."""
+    import numpy as np
+    counts = np.asarray(counts)
+    joined = isinstance(motifs, (str, bytes, bytearray))
+    parts = [motifs] if joined else list(motifs)
+    parts = [m if isinstance(m, str) else bytes(m).decode("ascii") for m in parts]
+    text = "".join(parts)
+    if counts.ndim != 2 or counts.shape[0] != len(text) or counts.shape[1] < 4:
+        raise ValueError(f"aligned_consensus needs the counts motif_align_path returned for these motifs: {counts.shape} for {len(text)} letters")
+    best = np.argmax(counts[:, :4], axis=1)                                   # the first of equal maxima
+    keep = counts[:, :4].max(axis=1, initial=0) == 0
+    new = np.where(keep, np.frombuffer(text.encode("ascii"), dtype=np.uint8), np.frombuffer(b"ACGT", dtype=np.uint8)[best])
+    new = new.astype(np.uint8).tobytes().decode("ascii")
+    if joined:
+        return new
+    out, at = [], 0
+    for m in parts:
+        out.append(new[at:at + len(m)])
+        at += len(m)
+    return out
+
+
+def path_copies(path_row, start, k):
+    """The copies of a row's alignment as rows of PATH_COPY_DTYPE (copy, start, end, subs, ins, dels): the positions are cut each
+    time the path enters the row's start column (path[0] & PATH_COLUMN) by an aligned position; `start` is the row's first
+    position, so start and end are positions of the range.  The deletions between two positions count with the copy of the position
+    in front of them.  The rows add up to the row: its positions, its SUB and INS entries and its deletions.  Host numpy."""
+    import numpy as np
+    p = np.asarray(path_row).astype(np.int64)
+    n = len(p)
+    if not n:
+        return np.zeros(0, dtype=PATH_COPY_DTYPE)
+    aligned = (p & PATH_INS) == 0
+    cuts = np.flatnonzero(aligned & ((p & PATH_COLUMN) == (p[0] & PATH_COLUMN)))
+    cuts = cuts[cuts > 0]
+    bounds = np.concatenate([[0], cuts, [n]])
+    dels = np.concatenate([path_deletions(p, k), [0]])
+    sub, ins = ((p & PATH_SUB) != 0) & aligned, ~aligned
+    out = np.zeros(len(bounds) - 1, dtype=PATH_COPY_DTYPE)
+    out["copy"] = np.arange(len(out))
+    out["start"], out["end"] = bounds[:-1] + int(start), bounds[1:] + int(start)
+    for field, what in (("subs", sub), ("ins", ins), ("dels", dels)):
+        out[field] = np.add.reduceat(what.astype(np.int64), bounds[:-1])
+    return out
+
+
+def refine_motifs(target, contig, begin, end, repeats, motifs, rounds=2, trace_bytes=0):
+    """TRF-style refinement: `rounds` times at most, align the repeats to their motifs (motif_align_path with counts) and take
+    the aligned consensus as the new motifs; stops early when no motif changes.  target: a Genome (contig is its contig) or a
+    Context (contig is then the sequence).  Returns (motifs as a list of str, the alignment of the last call, per repeat the
+    number of rounds that changed its motif).  The alignment is that of the returned motifs: if the last round still changed a
+    motif, the repeats are aligned once more."""
+    import numpy as np
+    _int_check("rounds", rounds, 1)
+    ks = np.asarray(repeats["k"]).tolist()
+    text = _motif_letters(motifs, ks).decode("ascii")
+    offsets = np.concatenate([[0], np.cumsum(ks)]).astype(np.int64).tolist()
+    current = [text[offsets[at]:offsets[at + 1]] for at in range(len(ks))]
+    changed = np.zeros(len(ks), dtype=np.uint32)
+
+    def call():
+        if isinstance(target, Context):
+            return target.motif_align_path(contig, repeats, current, begin, end, with_counts=True)
+        return target.motif_align_path(contig, begin, end, repeats, current, with_counts=True, trace_bytes=trace_bytes)
+
+    align, stale = None, True
+    for _ in range(rounds):
+        align, _paths, counts = call()
+        new = aligned_consensus(counts, current)
+        moved = np.array([a != b for a, b in zip(current, new)], dtype=bool)
+        stale = bool(moved.any())
+        if not stale:
+            break
+        changed += moved
+        current = new
+    if stale:
+        align = call()[0]
+    return current, align, changed
+
+
 def _link_paths(chains, links):
     """(paths, link_out, is_open) of the chains of period_chains (min_len = 0) and the links of period_links of the same window
     and settings: every chain has at most one link in and one out, so the links form paths.  paths: one list of chain indices per
@@ -1323,6 +1493,16 @@ class Genome:
         over, the least among those), start_column and end_column.  alignment_rows() derives the rest."""
         return _motif_align(self.ctx, (self, contig), begin, end, repeats, motifs, with_stats)
 
+    def motif_align_path(self, contig, begin, end, repeats, motifs, with_counts=False, with_stats=False, trace_bytes=0):
+        """motif_align WITH ITS PATH (prf_motif_align_path): the same rows, and per repeat one uint16 per position: the motif
+        column in PATH_COLUMN; PATH_INS: the position is an insertion behind that column; PATH_SUB: it is aligned to the column
+        and does not match it.  Deleted motif letters are read from the path (path_deletions, path_cigar).  Returns (rows, list
+        of paths), then with_counts an array of (sum of k, 6) per motif letter: the aligned positions that are A, C, G, T, the
+        deletions and the insertions of the column (aligned_consensus re-estimates the motifs from it), then the ScanStats
+        with_stats.  trace_bytes bounds the device scratch of one batch of repeats (0: the library's default); the results do
+        not depend on it."""
+        return _motif_align_path(self.ctx, (self, contig), begin, end, repeats, motifs, with_counts, with_stats, trace_bytes)
+
     @property
     def positions(self):
         return self.ctx.lib.prf_genome_positions(self._h)
@@ -1547,6 +1727,10 @@ class Context:
     def motif_align(self, seq, repeats, motifs, begin=0, end=None, with_stats=False):
         """Genome.motif_align for one sequence (str or bytes) in one call: load, align, free (prf_motif_align_seq)."""
         return _motif_align(self, seq, begin, end, repeats, motifs, with_stats)
+
+    def motif_align_path(self, seq, repeats, motifs, begin=0, end=None, with_counts=False, with_stats=False):
+        """Genome.motif_align_path for one sequence (str or bytes) in one call: load, align, free (prf_motif_align_path_seq)."""
+        return _motif_align_path(self, seq, begin, end, repeats, motifs, with_counts, with_stats, 0)
 
     def period_links(self, seq, kmin, kmax, min_seed, max_gap, max_shift, n_matches=False, begin=0, end=None, positions=None,
                      with_stats=False):

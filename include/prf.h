@@ -374,6 +374,11 @@ int prf_measure_hbm_read(prf_ctx *ctx, uint64_t bytes, int iters, double *gbps);
  * here; prf_scan_stats.path = 14 is theirs. */
 #include "prf_align.h"
 
+/* ---- ... and the alignment itself: the path through the dynamic programming, one entry per position, and the counts of the
+ * aligned columns: three more entry points, additions to ABI version 4, declared in prf_alignpath.h, which this header
+ * includes here; prf_scan_stats.path = 15 is theirs. */
+#include "prf_alignpath.h"
+
 #ifdef __cplusplus
 }
 #endif
