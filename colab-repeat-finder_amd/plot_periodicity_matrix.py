@@ -24,6 +24,9 @@ the best alignment of the whole repeat to the endless repetition of the motif, t
 --align-path adds the alignment itself as a CIGAR, --refine R re-estimates each motif from its aligned copies and aligns again,
 --copies-tsv lists where each copy begins and ends and what it differs in:
     plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --groups-tsv vntr.tsv --min-seed 12 --max-gap 8 --max-shift 4 --group-consensus --align --align-path --refine 2 --copies-tsv copies.tsv
+--extend F gives every repeat SCORED BOUNDARIES: the best local alignment of the repeat padded by F positions on both sides against
+the endless repetition of its motif, under --weights match,mismatch,indel (TRF's 2,7,7 by default); --min-score filters by it:
+    plot_periodicity_matrix.py genome.fa -i chr22:0-50818468 --max-motif-size 1000 --groups-tsv vntr.tsv --min-seed 12 --max-gap 8 --max-shift 4 --group-consensus --extend 50 --min-score 50
 """
 import argparse
 import os
@@ -93,7 +96,28 @@ def build_parser():
     p.add_argument("--copies-tsv", help="With --align: also write one line per aligned copy of every listed repeat: chrom, start, "
                                         "end and period of the repeat, the copy's number, start and end, its substitutions, "
                                         "insertions and deletions.")
+    p.add_argument("--extend", type=int, metavar="F", help="With --consensus or --group-consensus: append three columns per repeat: "
+                   "ext_start, ext_end and score of the best local alignment of the repeat padded by F positions on both sides "
+                   "against the endless repetition of its motif; of equal scores the alignment that ends first and begins last.  A "
+                   "'.' in all three: a repeat above a limit of one alignment.  A score of 0: nothing matches, and the interval is "
+                   "the repeat's own.")
+    p.add_argument("--weights", metavar="M,X,G", help="With --extend: the score is M * matches - X * substitutions - G * (insertions "
+                   "+ deletions); each 1 .. 16 (default: 2,7,7).")
+    p.add_argument("--min-score", type=int, metavar="S", help="With --extend: keep repeats of at least this score.")
     return p
+
+
+def parse_weights(text, parser):
+    """(match, mismatch, indel) of --weights M,X,G."""
+    if text is None:
+        return 2, 7, 7
+    if not re.fullmatch(r"\d+,\d+,\d+", text):
+        parser.error(f"--weights is set to {text!r}. It must be three numbers match,mismatch,indel, such as 2,7,7.")
+    weights = tuple(int(w) for w in text.split(","))
+    for name, w in zip(("match", "mismatch", "indel"), weights):
+        if not 1 <= w <= 16:
+            parser.error(f"--weights: {name} is set to {w}. It must be 1 .. 16.")
+    return weights
 
 
 def check_chain_args(args, parser):
@@ -128,6 +152,16 @@ def check_chain_args(args, parser):
                 parser.error(f"--{name.replace('_', '-')} belongs to --align")
     if not 0 <= args.refine <= 100:
         parser.error(f"--refine is set to {args.refine}. It must be 0 .. 100.")
+    if args.extend is None:
+        for name in ("weights", "min_score"):
+            if getattr(args, name) is not None:
+                parser.error(f"--{name.replace('_', '-')} belongs to --extend")
+    else:
+        if not (args.consensus or args.group_consensus):
+            parser.error("--extend needs the motifs of --consensus (with --chains-tsv) or --group-consensus (with --groups-tsv)")
+        if args.extend < 0:
+            parser.error(f"--extend is set to {args.extend}. It must be at least 0.")
+        args.weights = parse_weights(args.weights, parser)
     if not args.groups_tsv:
         if args.max_shift is not None:
             parser.error("--max-shift belongs to --groups-tsv")
@@ -293,6 +327,42 @@ def with_alignments(args, lines, aligned, fits, detail=None):
     return lines
 
 
+def extended_of(genome, begin, end, rows, motifs, flank, weights):
+    """(rows of prf_native.local_rows, which of them were sent) of rows with the fields start and end against one motif each: the
+    window of every row within the limits of one alignment (and with a motif) is the row padded by `flank`
+    (prf_native.flank_repeats), sent in batches that respect the limits of one call; the others keep their interval and score 0."""
+    import numpy as np
+    import prf_native
+    table = np.zeros(len(rows), dtype=prf_native.REPEAT_DTYPE)
+    table["start"], table["end"], table["k"] = rows["start"], rows["end"], [len(m) for m in motifs]
+    windows, fits = prf_native.flank_repeats(table, flank, end - begin)
+    sent = np.flatnonzero(fits)
+    local = np.zeros(len(rows), dtype=prf_native.LOCAL_ALIGNMENT_DTYPE)
+    for a, b in consensus_batches(table["k"][sent].tolist(), prf_native.CONSENSUS_MAX_ROWS, prf_native.CONSENSUS_MAX_LETTERS):
+        local[sent[a:b]] = genome.motif_align_local(0, begin, end, windows[sent[a:b]], [motifs[at] for at in sent[a:b].tolist()], *weights)
+    return prf_native.local_rows(table, windows, local), fits
+
+
+def with_extensions(args, begin, lines, extended, fits):
+    """The lines with the three columns of --extend, in the file's coordinates, without those --min-score drops (a row above a
+    limit among them)."""
+    more = [f"\t{begin + first}\t{begin + last}\t{score}\n" if ok else "\t.\t.\t.\n"
+            for ok, first, last, score in zip(fits.tolist(), *(extended[f].tolist() for f in ("local_start", "local_end", "score")))]
+    lines = [line[:-1] + tail for line, tail in zip(lines, more)]
+    if args.min_score is not None:
+        keep = (fits & (extended["score"] >= args.min_score)).tolist()
+        lines = [line for line, kept in zip(lines, keep) if kept]
+    return lines
+
+
+def aligned_kept(args, aligned, fits):
+    """Which rows with_alignments keeps."""
+    import numpy as np
+    if args.min_aligned_identity is None:
+        return np.ones(len(fits), dtype=bool)
+    return fits & (aligned["aligned_identity"] >= args.min_aligned_identity)
+
+
 def wants_paths(args):
     return bool(args.align_path or args.refine or args.copies_tsv)
 
@@ -382,6 +452,8 @@ def list_chains(args, chrom, seq, begin, end, context=None):
                 motifs = detail["motifs"]                           # of the last round of --refine
             elif args.align:
                 aligned, fits = aligned_of(genome, begin, end, rows, motifs)
+            if args.extend is not None:
+                extended, extends = extended_of(genome, begin, end, rows, motifs, args.extend, args.weights)
     finally:
         genome.free()
     lines = list(chain_lines(chrom, begin, seq, rows))
@@ -393,10 +465,16 @@ def list_chains(args, chrom, seq, begin, end, context=None):
             if args.align:
                 aligned, fits = aligned[np.array(keep, dtype=bool)], fits[np.array(keep, dtype=bool)]
                 detail = take_detail(detail, keep) if detail is not None else None
+            if args.extend is not None:
+                extended, extends = extended[np.array(keep, dtype=bool)], extends[np.array(keep, dtype=bool)]
         if args.align:
             lines = with_alignments(args, lines, aligned, fits, detail)
             if args.copies_tsv:
                 write_copies(args, chrom, begin, aligned, fits, detail)
+            if args.extend is not None:
+                extended, extends = extended[aligned_kept(args, aligned, fits)], extends[aligned_kept(args, aligned, fits)]
+        if args.extend is not None:
+            lines = with_extensions(args, begin, lines, extended, extends)
     with open(args.chains_tsv, "wt") as out:
         out.writelines(lines)
     print(f"Wrote {args.chains_tsv}: {len(lines)} repeats")
@@ -489,6 +567,8 @@ def list_groups(args, chrom, seq, begin, end, context=None):
                 motifs = detail["motifs"]                           # of the last round of --refine
             elif args.align:
                 aligned, fits = aligned_of(genome, begin, end, rows, motifs)
+            if args.extend is not None:                         # the group's [start, end) plus the flank against the motif of its chosen piece
+                extended, extends = extended_of(genome, begin, end, rows, motifs, args.extend, args.weights)
     finally:
         genome.free()
     lines = list(group_lines(chrom, begin, seq, rows))
@@ -500,10 +580,16 @@ def list_groups(args, chrom, seq, begin, end, context=None):
             if args.align:
                 aligned, fits = aligned[np.array(passed, dtype=bool)], fits[np.array(passed, dtype=bool)]
                 detail = take_detail(detail, passed) if detail is not None else None
+            if args.extend is not None:
+                extended, extends = extended[np.array(passed, dtype=bool)], extends[np.array(passed, dtype=bool)]
         if args.align:
             lines = with_alignments(args, lines, aligned, fits, detail)
             if args.copies_tsv:
                 write_copies(args, chrom, begin, aligned, fits, detail)
+            if args.extend is not None:
+                extended, extends = extended[aligned_kept(args, aligned, fits)], extends[aligned_kept(args, aligned, fits)]
+        if args.extend is not None:
+            lines = with_extensions(args, begin, lines, extended, extends)
     with open(args.groups_tsv, "wt") as out:
         out.writelines(lines)
     print(f"Wrote {args.groups_tsv}: {len(lines)} repeats")

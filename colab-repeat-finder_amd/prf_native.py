@@ -206,6 +206,13 @@ PATH_SUB = 0x4000                    # PRF_PATH_SUB: the position is aligned to 
 PATH_COLUMN = 0x03FF                 # PRF_PATH_COLUMN
 # what path_copies returns per copy
 PATH_COPY_DTYPE = [("copy", "<u4"), ("start", "<u8"), ("end", "<u8"), ("subs", "<u4"), ("ins", "<u4"), ("dels", "<u4")]
+# the entry points of the local alignment of windows to motifs (include/prf_alignlocal.h, which prf.h includes)
+ALIGNLOCAL_EXPORTS = ["prf_motif_align_local", "prf_motif_align_local_seq"]
+LOCAL_ALIGNMENT_DTYPE = [("score", "<u4"), ("first", "<u4"), ("end", "<u4"), ("start_column", "<u4"), ("end_column", "<u4"),
+                         ("reserved", "<u4")]                                                                 # prf_local_alignment, 24 bytes
+ALIGNLOCAL_MAX_WEIGHT = 16           # PRF_ALIGNLOCAL_MAX_WEIGHT: each of match, mismatch, indel
+# what local_rows appends to its rows
+LOCAL_FIELDS = [("local_start", "<u8"), ("local_end", "<u8"), ("score", "<u4")]
 DIRECTIONS = {"main": 1, "anti": 2, "both": 3}
 DOT_LAUNCH_CELLS = 1 << 36   # PRF_DOT_LAUNCH_CELLS
 DOT_MAX_CELLS = 1 << 42      # PRF_DOT_MAX_CELLS
@@ -357,6 +364,10 @@ def load_library():
         lib.prf_motif_align_path.argtypes = [vp, vp, ctypes.c_uint32] + path_tail
         lib.prf_motif_align_path_ex.argtypes = [vp, vp, ctypes.c_uint32] + path_tail + [ctypes.c_uint64]
         lib.prf_motif_align_path_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + path_tail
+        # begin, end, rows, n_rows, motifs, letters_length, match, mismatch, indel, dst, stats
+        local_tail = align_tail[:6] + [ctypes.c_uint32] * 3 + align_tail[6:]
+        lib.prf_motif_align_local.argtypes = [vp, vp, ctypes.c_uint32] + local_tail
+        lib.prf_motif_align_local_seq.argtypes = [vp, ctypes.POINTER(_Contig)] + local_tail
         lib.prf_free_ihits.restype = None
         lib.prf_free_hits.restype = None
         lib.prf_measure_hbm_read.argtypes = [vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -851,6 +862,89 @@ def alignment_rows(rows, align):
     out["aligned_matches"] = n - out["subs"] - out["ins"]
     out["aligned_identity"] = out["aligned_matches"] / np.maximum(n + out["del"], 1)
     out["aligned_copies"] = consumed / np.maximum(rows[k_field].astype(np.int64), 1)
+    return out
+
+
+def _local_weights(match, mismatch, indel):
+    for name, w in (("match", match), ("mismatch", mismatch), ("indel", indel)):
+        _int_check(name, w, 1)
+        if w > ALIGNLOCAL_MAX_WEIGHT:
+            raise ValueError(f"{name} = {w} is more than a local alignment takes ({ALIGNLOCAL_MAX_WEIGHT})")
+    return int(match), int(mismatch), int(indel)
+
+
+def _motif_align_local(ctx, target, begin, end, repeats, motifs, match, mismatch, indel, with_stats):
+    """The motif_align_local calls.  target: (genome, contig) or one sequence.  Returns the rows of LOCAL_ALIGNMENT_DTYPE, then
+    the ScanStats with_stats."""
+    import numpy as np
+    weights = _local_weights(match, mismatch, indel)
+    where, c_end, keep, rows, n_rows, letters = _repeat_table(target, begin, end, repeats)
+    if n_rows:
+        k, length = rows["k"][:n_rows], rows["end"][:n_rows] - rows["start"][:n_rows]
+        if (k > ALIGN_MAX_K).any():
+            at = int(np.argmax(k > ALIGN_MAX_K))
+            raise ValueError(f"repeat {at}: k = {k[at]} is more than an alignment takes ({ALIGN_MAX_K})")
+        if (length > ALIGN_MAX_LEN).any():
+            at = int(np.argmax(length > ALIGN_MAX_LEN))
+            raise ValueError(f"repeat {at}: {length[at]} positions are more than an alignment takes ({ALIGN_MAX_LEN})")
+    text = _motif_letters(motifs, rows["k"][:n_rows].tolist())
+    out = np.zeros(max(1, n_rows), dtype=LOCAL_ALIGNMENT_DTYPE)
+    stats = ScanStats()
+    if keep is not None:
+        fn, head = ctx.lib.prf_motif_align_local_seq, (ctx._h,)
+    else:
+        fn, head = ctx.lib.prf_motif_align_local, (ctx._h, target[0]._h)
+    _check(ctx.lib, fn(*head, *where, begin, c_end, rows.ctypes.data, n_rows, text, len(text), *weights, out.ctypes.data, ctypes.byref(stats)))
+    got = out[:n_rows].copy()
+    return (got, stats) if with_stats else got
+
+
+def flank_repeats(repeats, flank, n):
+    """The WINDOWS motif_align_local searches around found repeats: rows with the fields start, end and k -- or period -- of a
+    range of n positions, each padded by `flank` on both sides and clipped to the range: (max(0, start - flank), min(n, end +
+    flank), k) as REPEAT_DTYPE.  Where the window would hold more than ALIGN_MAX_LEN positions the flank is cut down to what
+    fits, the same on both sides (one more in front if what fits is odd) before the clipping.  Returns (windows, sent): sent[i]
+    is False for a row whose own length or k is above a limit (ALIGN_MAX_LEN, ALIGN_MAX_K); its window is the row itself and must
+    not be sent.  Host numpy."""
+    import numpy as np
+    _int_check("flank", flank, 0)
+    _int_check("n", n, 0)
+    k_field = "k" if "k" in repeats.dtype.names else "period"
+    start, stop, k = (repeats[name].astype(np.int64) for name in ("start", "end", k_field))
+    if len(start) and ((start < 0) | (start >= stop) | (stop > n)).any():
+        at = int(np.argmax((start < 0) | (start >= stop) | (stop > n)))
+        raise ValueError(f"repeat {at}: [{start[at]}, {stop[at]}) is not a stretch of the range's {n} positions")
+    length = stop - start
+    sent = (length <= ALIGN_MAX_LEN) & (k <= ALIGN_MAX_K) & (k >= 1)
+    room = np.clip(ALIGN_MAX_LEN - length, 0, 2 * int(flank))                   # what both flanks may add together
+    behind = np.where(sent, np.minimum(int(flank), room // 2), 0)
+    front = np.where(sent, np.minimum(int(flank), room - behind), 0)
+    windows = np.zeros(len(start), dtype=REPEAT_DTYPE)
+    windows["start"], windows["end"], windows["k"] = np.maximum(0, start - front), np.minimum(int(n), stop + behind), np.clip(k, 0, 0xFFFFFFFF)
+    return windows, sent
+
+
+def local_rows(rows, windows, local):
+    """Rows with the fields start and end, with what motif_align_local says of their windows (flank_repeats), in their order: the
+    fields of `rows`, then LOCAL_FIELDS: local_start = the window's start + first and local_end = the window's start + end,
+    relative to the range like start and end, and score.  A row with score 0, or one not sent (flank_repeats; its row of `local`
+    stays all zeros), keeps its own interval and score 0.  Host numpy."""
+    import numpy as np
+    if not len(rows) == len(windows) == len(local):
+        raise ValueError("local_rows needs the windows of these rows and the rows motif_align_local returned for them")
+    out = np.zeros(len(rows), dtype=rows.dtype.descr + LOCAL_FIELDS)
+    for name in rows.dtype.names:
+        out[name] = rows[name]
+    score = local["score"].astype(np.int64)
+    took = score > 0
+    w_start = windows["start"].astype(np.int64)
+    if len(rows) and took.any():
+        first, end = local["first"].astype(np.int64), local["end"].astype(np.int64)
+        if ((first >= end) | (w_start + end > windows["end"].astype(np.int64)))[took].any():
+            raise ValueError("local_rows needs the windows of these rows and the rows motif_align_local returned for them")
+    out["local_start"] = np.where(took, w_start + local["first"], rows["start"])
+    out["local_end"] = np.where(took, w_start + local["end"], rows["end"])
+    out["score"] = np.where(took, score, 0)
     return out
 
 
@@ -1503,6 +1597,16 @@ class Genome:
         not depend on it."""
         return _motif_align_path(self.ctx, (self, contig), begin, end, repeats, motifs, with_counts, with_stats, trace_bytes)
 
+    def motif_align_local(self, contig, begin, end, repeats, motifs, match=2, mismatch=7, indel=7, with_stats=False):
+        """The best LOCAL alignment of windows of positions [begin, end) of a contig against the endless repetition of their
+        motifs (prf_motif_align_local), scored match * matches - mismatch * substitutions - indel * (insertions + deletions),
+        each weight 1 .. ALIGNLOCAL_MAX_WEIGHT.  repeats: the windows, as motif_align takes its repeats (flank_repeats pads found
+        repeats).  Returns a numpy structured array in the order of the windows with the fields score, first and end (relative
+        to the window's start), start_column and end_column; of equal scores the alignment that ends first and begins last; all
+        zeros where nothing matches.  motif_align on (start + first, start + end, k) with the same motif gives the refined
+        interval's edits and copies; local_rows() puts the intervals beside their rows."""
+        return _motif_align_local(self.ctx, (self, contig), begin, end, repeats, motifs, match, mismatch, indel, with_stats)
+
     @property
     def positions(self):
         return self.ctx.lib.prf_genome_positions(self._h)
@@ -1731,6 +1835,10 @@ class Context:
     def motif_align_path(self, seq, repeats, motifs, begin=0, end=None, with_counts=False, with_stats=False):
         """Genome.motif_align_path for one sequence (str or bytes) in one call: load, align, free (prf_motif_align_path_seq)."""
         return _motif_align_path(self, seq, begin, end, repeats, motifs, with_counts, with_stats, 0)
+
+    def motif_align_local(self, seq, repeats, motifs, begin=0, end=None, match=2, mismatch=7, indel=7, with_stats=False):
+        """Genome.motif_align_local for one sequence (str or bytes) in one call: load, align, free (prf_motif_align_local_seq)."""
+        return _motif_align_local(self, seq, begin, end, repeats, motifs, match, mismatch, indel, with_stats)
 
     def period_links(self, seq, kmin, kmax, min_seed, max_gap, max_shift, n_matches=False, begin=0, end=None, positions=None,
                      with_stats=False):

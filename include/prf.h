@@ -378,6 +378,7 @@ int prf_measure_hbm_read(prf_ctx *ctx, uint64_t bytes, int iters, double *gbps);
  * aligned columns: three more entry points, additions to ABI version 4, declared in prf_alignpath.h, which this header
  * includes here; prf_scan_stats.path = 15 is theirs. */
 #include "prf_alignpath.h"
+#include "prf_alignlocal.h"
 
 #ifdef __cplusplus
 }
